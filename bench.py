@@ -11,6 +11,12 @@ relations: radix partition, sort, merge-join count (N>1: range partition, an
 RCCL all-to-all over xGMI, then the local join and an all-reduce of the
 count).  Inputs are generated in HBM before the timed region.
 
+A plain run sets up, warms up, times --steps steps and prints the line
+(value, ms_per_step, the match count).  --full adds what takes runs or
+passes of its own: the untimed per-kernel breakdown and the dominant kernel's
+roofline, the check of the sorted outputs and the CPU baseline.
+--dump-outputs DIR writes the last timed step's outputs as .npy files.
+
 Prints ONE JSON line (rank 0).  See DESIGN.md §7 for the fields.
 """
 import argparse
@@ -141,14 +147,27 @@ def parse():
     p.add_argument("--fanout-bits", type=int, default=8,
                    help="level-1 partitions (2^bits) of the join; the library raises it "
                         "as the relation size needs")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline figure: the untimed per-kernel "
+                        "breakdown and the dominant kernel's roofline (HIP events in the "
+                        "timed steps), the output check and the CPU baseline.  Without it "
+                        "a run sets up, warms up, times --steps steps and prints the line "
+                        "(roofline, cpu_baseline and output_check are then null/skipped; "
+                        "result_ok is the match count alone)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step returned as "
+                        "DIR/<name>.npy (float64: the match count, key and payload columns "
+                        "of the outputs; a fixed seeded sample of the rows of a large "
+                        "output, 64 MB at most in all)")
     p.add_argument("--cpu-n", type=int, default=128_000_000,
-                   help="tuples per relation of the bounded CPU-baseline sample")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+                   help="--full: tuples per relation of the bounded CPU-baseline sample")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="--full without the CPU baseline")
     p.add_argument("--no-trace", action="store_true",
-                   help="lab: no per-kernel HIP events in the timed loop (measures what "
-                        "the trace costs; the line then has no roofline)")
+                   help="lab, with --full: no per-kernel HIP events in the timed loop "
+                        "(measures what the trace costs; the line then has no roofline)")
     p.add_argument("--no-check", action="store_true",
-                   help="skip the output check after the timed loop (default: the sorted "
+                   help="--full without the output check after the timed loop (the sorted "
                         "outputs are checked on the device for (key, payload) order and "
                         "against the inputs' order-independent checksum; result_ok "
                         "carries it)")
@@ -172,7 +191,12 @@ def parse():
                         "(relation_t over device-resident tuples, no key-range hint: the "
                         "plan is derived from |R| as the reference does) instead of "
                         "smj_dev_join")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps needs at least 1 timed step, --warmup 0 or more")
+    if a.dump_outputs and a.op == "exchange":
+        p.error("--dump-outputs: --op exchange times a transfer and returns no arrays")
+    return a
 
 
 # --------------------------------------------------------------------------
@@ -204,6 +228,21 @@ def _ref_exe(name):
             f"{exe} missing: run oracle/build_ref.sh where /root/reference exists "
             "(or pass --no-cpu-baseline)")
     return exe
+
+
+def _baseline_or_absent(fn, *args):
+    """--full's CPU baseline; where the reference binaries were never built
+    (no reference sources on the build host) the line says so instead of a
+    figure, and stderr carries the reason."""
+    try:
+        return fn(*args)
+    except FileNotFoundError as e:
+        print(f"[bench] no CPU baseline: {e}", file=sys.stderr, flush=True)
+        return {"value": None, "unit": "Mtuples/s", "kind": "absent", "error": str(e)}
+
+
+def _skipped(a):
+    return "skipped (--no-check)" if a.full else "skipped (the outputs are checked with --full)"
 
 
 def host_cores():
@@ -414,6 +453,47 @@ def output_check(pairs, w, dist=None):
     return res
 
 
+DUMP_ROWS = 1 << 20  # sampled rows of a large output (8 MB a float64 column)
+
+
+def _f64_columns(name, v):
+    """float64 arrays of an integer tensor, exact: a value within +-2^53 as
+    itself, a wider column (random 64-bit payloads) as its signed high and
+    unsigned low 32-bit halves."""
+    v = v.to(torch.int64).cpu()
+    if v.numel() == 0 or (int(v.min()) >= -(1 << 53) and int(v.max()) <= 1 << 53):
+        return {name: v.to(torch.float64).numpy()}
+    return {name + "_hi32": (v >> 32).to(torch.float64).numpy(),
+            name + "_lo32": (v & 0xFFFFFFFF).to(torch.float64).numpy()}
+
+
+def dump_outputs(outdir, outs, suffix=""):
+    """--dump-outputs: {name: value} of what the last timed step returned ->
+    outdir/<name><suffix>.npy, float64.  A number or a 1-D tensor is written
+    whole (sampled like the rows when longer than DUMP_ROWS); a relation
+    ((n, 2) rows of payload, key) as <name>_key and <name>_payload: every row
+    up to DUMP_ROWS, else the DUMP_ROWS rows at sorted positions drawn by a
+    generator seeded with the row count, the same in every run and build."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {}
+    for name, v in outs.items():
+        if not torch.is_tensor(v):
+            arrays[name] = np.asarray([v], dtype=np.float64)
+            continue
+        n = v.shape[0]
+        if n > DUMP_ROWS:
+            idx = np.sort(np.random.default_rng(n).integers(0, n, DUMP_ROWS))
+            v = v.index_select(0, torch.from_numpy(idx).to(v.device))
+        if v.dim() == 1:
+            arrays.update(_f64_columns(name, v))
+        else:
+            arrays.update(_f64_columns(name + "_key", v[:, 1]))
+            arrays.update(_f64_columns(name + "_payload", v[:, 0]))
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), arr)
+
+
 # --------------------------------------------------------------------------
 def _json_stdout():
     """stdout carries exactly the one JSON line: native libraries (RCCL
@@ -566,7 +646,7 @@ def main():
         elif exchange:
             dj.stats_reset()
 
-    elapsed, kern, brk = timed_loop(a, tracer, dist, step, reset)
+    elapsed, kern, brk = timed_loop(a, tracer, dist, step, reset, breakdown=a.full)
     # the intermediate layout the last step ran in (the 1-GPU join: p48 for
     # row-id payloads, words or tuples for wider ones)
     layout = None if exchange else lib.last_layout(api=a.api)
@@ -610,12 +690,22 @@ def main():
     # checksums against the inputs); the reference-named entry point keeps its
     # sorted relations internal, so --api checks the count only
     chk = None
-    if not a.no_check and not (a.api and not exchange):
+    check = a.full and not a.no_check
+    outs = None
+    if (check or a.dump_outputs) and not (a.api and not exchange):
         if exchange and a.impl == "c":
             last = list(comm.sorted())
         outs = (sR, sS) if not exchange else tuple(last)
+    if check and outs is not None:
         chk = output_check([(R, outs[0]), (S, outs[1])], w, dist if exchange and N > 1 else None)
         ok = ok and chk["sorted"] and chk["checksum_equal"]
+    if a.dump_outputs:
+        # what the caller of the timed path holds after the last step: the
+        # match count and (except behind --api) the two sorted relations
+        named = {"matches": got}
+        if outs is not None:
+            named.update(sorted_R=outs[0], sorted_S=outs[1])
+        dump_outputs(a.dump_outputs, named, f"_rank{rank}" if N > 1 else "")
     ms_step = elapsed / a.steps * 1e3
     value = 2 * total / (elapsed / a.steps) / 1e6
 
@@ -631,8 +721,9 @@ def main():
     pipeline_gbs = 5 * 2 * total * w / (elapsed / a.steps) / 1e9
 
     cpu = None
-    if N == 1 and not a.no_cpu_baseline:
-        cpu = cpu_baseline(w, a.cpu_n, a.theta if a.dist == "zipf" else 0.0)
+    if a.full and N == 1 and not a.no_cpu_baseline:
+        cpu = _baseline_or_absent(cpu_baseline, w, a.cpu_n,
+                                  a.theta if a.dist == "zipf" else 0.0)
 
     strong = a.n_total is not None
     out = {
@@ -672,7 +763,7 @@ def main():
         "matches": got,
         "output_check": chk if chk is not None else
         ("count only (--api: the entry point keeps its sorted relations internal)"
-         if a.api else "skipped (--no-check)"),
+         if a.api else _skipped(a)),
         "detail": {
             "S_tuples_per_s_M": round(total / (elapsed / a.steps) / 1e6, 2),
             "pipeline_alg_GBps_5w": round(pipeline_gbs, 1),
@@ -748,15 +839,24 @@ def run_threads_join(a, json_out):
         acc["rows"] = [[0.0] * (len(PHASES) + 2) for _ in range(N)]
     step()  # the group's setup (communicators, buffers) stays out of the timing
     tracer = _WsTracer(lib, lib.lib.smj_mgpu_group_workspace(0))
-    elapsed, kern, brk = timed_loop(a, tracer, None, step, reset)
+    elapsed, kern, brk = timed_loop(a, tracer, None, step, reset, breakdown=a.full)
     k = max(acc["steps"], 1)
     xchg = {"impl": "c (smj_mgpu_join_slices: one process, one host thread per GPU)",
             **rank_phases([[v / k for v in r] for r in acc["rows"]]),
             "exchange_layout": acc["layout"], "xgmi_peak_GBps": 7 * 153}
     got = last["count"]
     ok = got == total
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"matches": got})
+        for g in range(N):
+            dev = torch.device("cuda", g)
+            with torch.cuda.device(dev):
+                outs = lib.mgpu_last_sorted(g, dev)
+                dump_outputs(a.dump_outputs, {"sorted_R": outs[0], "sorted_S": outs[1]},
+                             f"_rank{g}")
+                del outs
     chk = None
-    if not a.no_check:
+    if a.full and not a.no_check:
         # every rank's sorted shares: sorted, one key range per rank in rank
         # order, and together a permutation of the inputs (checksums)
         chk = {"sorted": True, "checksum_equal": True, "ranks_in_key_order": True}
@@ -813,7 +913,7 @@ def run_threads_join(a, json_out):
         "cpu_baseline": None,
         "result_ok": ok,
         "matches": got,
-        "output_check": chk if chk is not None else "skipped (--no-check)",
+        "output_check": chk if chk is not None else _skipped(a),
         "detail": {
             "S_tuples_per_s_M": round(total / (elapsed / a.steps) / 1e6, 2),
             "pipeline_alg_GBps_5w_per_gpu": round(5 * 2 * total * w / N / (elapsed / a.steps)
@@ -847,25 +947,32 @@ class _WsTracer:
             self.lib._ws = saved
 
 
-def timed_loop(a, lib, dist, step, reset=None):
+def timed_loop(a, lib, dist, step, reset=None, breakdown=True):
     """W untimed warm-up steps and a few untimed steps with every kernel
     traced (the per-kernel breakdown, which also names the dominant kernel),
     then exactly K steps between a barrier + synchronize on both sides with
     only the dominant kernel traced (one HIP event pair per launch: the other
     kernels' events would perturb the step).  Returns (max-over-ranks
     seconds, {dominant kernel: (ms, launches)} over the timed steps,
-    {kernel: ms per step} of the untimed breakdown)."""
+    {kernel: ms per step} of the untimed breakdown).
+
+    breakdown=False (a run without --full): the warm-up and the K timed
+    steps only, nothing traced; both dicts come back empty."""
     for _ in range(a.warmup):
         step()
-    nb = max(1, min(a.steps, 3))
-    lib.trace(not a.no_trace)
-    for _ in range(nb):
-        step()
-    torch.cuda.synchronize()
-    brk_l = {k: (v[0] / nb, v[1] / nb) for k, v in lib.trace_read().items()}
-    brk = {k: v[0] for k, v in brk_l.items()}
-    dom = max(brk, key=brk.get) if brk else None
-    lib.trace(False)
+    brk_l, dom = {}, None
+    if breakdown:
+        nb = max(1, min(a.steps, 3))
+        lib.trace(not a.no_trace)
+        for _ in range(nb):
+            step()
+        torch.cuda.synchronize()
+        brk_l = {k: (v[0] / nb, v[1] / nb) for k, v in lib.trace_read().items()}
+        brk = {k: v[0] for k, v in brk_l.items()}
+        dom = max(brk, key=brk.get) if brk else None
+        lib.trace(False)
+    else:
+        torch.cuda.synchronize()
     if dist:
         dist.barrier()
     if reset:
@@ -974,7 +1081,7 @@ def run_exchange(a, json_out, N, rank, local):
 
         def trace_read(self):
             return {}
-    elapsed, _, _ = timed_loop(a, _NoTrace(), dist if N > 1 else None, step)
+    elapsed, _, _ = timed_loop(a, _NoTrace(), dist if N > 1 else None, step, breakdown=a.full)
     t = elapsed / a.steps
     sent = row * (sum(sl) - sl[rank])  # this rank's bytes to other ranks per step
     recv = row * (sum(rl) - rl[rank])
@@ -1037,7 +1144,7 @@ def run_exchange_device_side(a, json_out, lib, n, w):
 
     def step():
         res["x"] = dj._exchange(S, "S")
-    elapsed, kern, brk = timed_loop(a, lib, None, step)
+    elapsed, kern, brk = timed_loop(a, lib, None, step, breakdown=a.full)
     xb, cap = dj.last_rows["S"][0], dj.last_rows["S"][1]
     eb = row_bytes(xb)
     lay = res["x"][-1]  # the layout the attempt ended in
@@ -1087,23 +1194,30 @@ def run_exchange_device_side(a, json_out, lib, n, w):
     print(json.dumps(out), file=json_out, flush=True)
 
 
+def partition_rows(out, hist, off, with_pid=False):
+    """The tuples of partition_relation_optimized's padded output in
+    partition order, without the padding (and each row's partition)."""
+    n = int(hist.sum().item())
+    pid = torch.repeat_interleave(torch.arange(hist.shape[0], device=hist.device), hist)
+    base = torch.cumsum(hist, 0) - hist
+    pos = off[pid] + torch.arange(n, device=hist.device) - base[pid]
+    # gathered in chunks: one 2^27-row gather of 16-byte rows exceeds the
+    # launch configuration torch's index kernel accepts on this part
+    rows = torch.empty((n,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device)
+    for i in range(0, n, 1 << 24):
+        rows[i:i + (1 << 24)] = out.index_select(0, pos[i:i + (1 << 24)])
+    return (rows, pid) if with_pid else rows
+
+
 def partition_check(R, out, hist, off, bits, shift, w):
     """partition_relation_optimized's output on the device: counts sum to n,
     every partition starts on a 64-byte boundary, every tuple of partition p
     has digit p (((key - 1) & mask) >> shift, partition.c:29), and the
     partitions together are a permutation of the input (checksums)."""
     n = R.shape[0]
-    fan = 1 << bits
     res = {"counts_sum": int(hist.sum().item()) == n,
            "aligned_64B": bool(((off * w) % 64 == 0).all().item())}
-    pid = torch.repeat_interleave(torch.arange(fan, device="cuda"), hist)
-    base = torch.cumsum(hist, 0) - hist
-    pos = off[pid] + torch.arange(n, device="cuda") - base[pid]
-    # gathered in chunks: one 2^27-row gather of 16-byte rows exceeds the
-    # launch configuration torch's index kernel accepts on this part
-    rows = torch.empty((n,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device)
-    for i in range(0, n, 1 << 24):
-        rows[i:i + (1 << 24)] = out.index_select(0, pos[i:i + (1 << 24)])
+    rows, pid = partition_rows(out, hist, off, with_pid=True)
     mask = ((1 << bits) - 1) << shift
     dig = ((rows[:, 1].to(torch.int64) - 1) & mask) >> shift
     res["digits"] = bool((dig == pid).all().item())
@@ -1160,10 +1274,19 @@ def run_op(a, lib, json_out, dist, N, rank):
         def step():
             lib.dev_partition(R, out, a.bits, a.shift, True, hist, off)
     torch.cuda.synchronize()
-    elapsed, kern, brk = timed_loop(a, lib, dist, step)
+    elapsed, kern, brk = timed_loop(a, lib, dist, step, breakdown=a.full)
     layout = lib.last_layout() if a.op == "sort" else None
+    if a.dump_outputs:
+        suffix = f"_rank{rank}" if N > 1 else ""
+        if a.op == "partition":
+            # the padded output's rows in partition order (the padding between
+            # partitions is not output), with the counts and offsets
+            dump_outputs(a.dump_outputs, {"hist": hist, "offsets": off,
+                                          "partitioned": partition_rows(out, hist, off)}, suffix)
+        else:
+            dump_outputs(a.dump_outputs, {"sorted" if a.op == "sort" else "merged": out}, suffix)
     chk = None
-    if a.no_check:
+    if a.no_check or not a.full:
         ok = True
     elif a.op == "sort":
         chk = output_check([(R, out)], w)
@@ -1184,8 +1307,9 @@ def run_op(a, lib, json_out, dist, N, rank):
                              cfg_key)
     alg = 2 * n * w  # 2·N·w for bench_sort and bench_partitioning
     cpu = None
-    if N == 1 and not a.no_cpu_baseline:
-        cpu = cpu_baseline_op(a.op, w, a.n if a.op == "merge" else n, a.bits, a.shift, a.fanin)
+    if a.full and N == 1 and not a.no_cpu_baseline:
+        cpu = _baseline_or_absent(cpu_baseline_op, a.op, w, a.n if a.op == "merge" else n,
+                                  a.bits, a.shift, a.fanin)
     ref = {"sort": "src/bench/sortbench.c:85-202 (avxsort_tuples)",
            "merge": "src/bench/multiwaymergebench.c:48-120 (avx_multiway_merge)",
            "partition": "src/bench/partitioningbench.c:128-196 (partition_relation_optimized)"}[a.op]
@@ -1216,7 +1340,7 @@ def run_op(a, lib, json_out, dist, N, rank):
         "roofline": roof,
         "cpu_baseline": cpu,
         "result_ok": ok,
-        "output_check": chk if chk is not None else "skipped (--no-check)",
+        "output_check": chk if chk is not None else _skipped(a),
         "detail": {
             "alg_GBps_2Nw": round(alg / (elapsed / a.steps) / 1e9, 1),
             "alg_frac_2Nw": round(alg / (elapsed / a.steps) / 1e9 / HBM_PEAK_GBS, 4),

@@ -34,6 +34,19 @@ JOIN_CASES = [("pk", 200000, 200000), ("pk", 300000, 100000),
               ("nonunique", 100000, 150000), ("zipf", 100000, 200000)]
 
 
+def savez_lzma(path, **arrays):
+    """numpy.savez with LZMA members, which numpy.load reads like any .npz:
+    the w8/w16 fixtures come to 0.75 MB each (deflate: 1.1 MB, above the
+    1 MiB a committed file may have)."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for name, arr in arrays.items():
+            buf = io.BytesIO()
+            np.save(buf, np.asanyarray(arr), allow_pickle=False)
+            z.writestr(name + ".npy", buf.getvalue())
+
+
 def join_inputs(gen, kind, nr, ns):
     """R and S of a join case; gen is oracle.Reference or oracle.Oracle."""
     gen.seed(12345)
@@ -152,7 +165,7 @@ def main():
         out["join_cases"] = np.array(cases, np.int64)
 
         path = os.path.join(HERE, f"golden_w{w}.npz")
-        np.savez_compressed(path, **out)
+        savez_lzma(path, **out)
         print(f"wrote {path} ({os.path.getsize(path) / 1e6:.2f} MB, {len(out)} arrays)")
 
 

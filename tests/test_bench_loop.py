@@ -86,6 +86,76 @@ def test_no_trace_lab_switch(no_cuda_sync):
     assert bench.dominant_roofline(kern, lambda name: 1.0, "none") is None
 
 
+def test_plain_run_times_only_its_steps(no_cuda_sync):
+    """Without --full (breakdown=False): the warm-up and exactly K timed
+    steps, no untimed breakdown, no kernel traced; no roofline follows."""
+    lib = FakeTraceLib()
+    a = types.SimpleNamespace(steps=7, warmup=2, no_trace=False)
+    n = [0]
+
+    def step():
+        n[0] += 1
+        lib.step()
+
+    elapsed, kern, brk = bench.timed_loop(a, lib, None, step, breakdown=False)
+    assert n[0] == 2 + 7
+    assert elapsed >= 0
+    assert kern == {} and brk == {}
+    assert not any(on for on, _ in lib.calls)
+    assert bench.dominant_roofline(kern, lambda name: 1.0, "none") is None
+    assert bench.step_phys(None, brk, 1.0, "none") == {}
+
+
+def test_full_is_an_option_off_by_default(monkeypatch):
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3",
+                                            "--warmup", "1"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 1)
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files, exact; a long output as the same
+    seeded sample of its rows in every run; 64-bit payloads in two halves."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(11)
+    small = torch.stack([torch.arange(5, 105), torch.arange(100, 0, -1)], 1)  # payload, key
+    bench.dump_outputs(str(tmp_path / "a"), {"matches": 100, "sorted_R": small})
+    got = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["matches.npy", "sorted_R_key.npy", "sorted_R_payload.npy"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["matches.npy"].tolist() == [100.0]
+    assert np.array_equal(got["sorted_R_key.npy"], small[:, 1].numpy())
+    assert np.array_equal(got["sorted_R_payload.npy"], small[:, 0].numpy())
+
+    monkeypatch.setattr(bench, "DUMP_ROWS", 64)
+    big = torch.stack([torch.randint(0, 1 << 62, (1000,), generator=g) * 2 - (1 << 62),
+                       torch.arange(1000)], 1)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"sorted_S": big}, "_rank1")
+    b = {p.name: np.load(p) for p in (tmp_path / "b").iterdir()}
+    c = {p.name: np.load(p) for p in (tmp_path / "c").iterdir()}
+    assert sorted(b) == ["sorted_S_key_rank1.npy", "sorted_S_payload_hi32_rank1.npy",
+                         "sorted_S_payload_lo32_rank1.npy"]
+    assert all(np.array_equal(b[k], c[k]) for k in b)
+    keys = b["sorted_S_key_rank1.npy"].astype(np.int64)
+    assert keys.shape == (64,) and (np.diff(keys) >= 0).all() and len(set(keys)) > 32
+    hi = b["sorted_S_payload_hi32_rank1.npy"].astype(np.int64)
+    lo = b["sorted_S_payload_lo32_rank1.npy"].astype(np.int64)
+    assert np.array_equal((hi << 32) | lo, big[keys, 0].numpy())
+    ext = torch.tensor([-(1 << 63), (1 << 63) - 1, -1, 0])
+    halves = bench._f64_columns("p", ext)
+    assert np.array_equal((halves["p_hi32"].astype(np.int64) << 32)
+                          | halves["p_lo32"].astype(np.int64), ext.numpy())
+    assert list(bench._f64_columns("p", torch.tensor([-(1 << 53), 1 << 53]))) == ["p"]
+
+
 def test_phys_fields(monkeypatch):
     """roofline.phys_frac = PMC bytes per launch / average launch time / peak
     beside the credited frac; the step's PMC bytes from every library kernel

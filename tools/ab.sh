@@ -19,7 +19,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
     for lb in $LIBS; do
       ln=${lb%%:*}; ld=${lb#*:}
       f=$O/${name}_${ln}_$r.json
-      SMJ_LIB_DIR=$PWD/$ld timeout -k 10 300 python3 bench.py ${args//,/ } --no-cpu-baseline --steps ${STEPS:-10} --warmup 2 > $f 2> $f.err || { echo "FAIL $name $ln"; tail -5 $f.err; exit 1; }
+      SMJ_LIB_DIR=$PWD/$ld timeout -k 10 300 python3 bench.py --full ${args//,/ } --no-cpu-baseline --steps ${STEPS:-10} --warmup 2 > $f 2> $f.err || { echo "FAIL $name $ln"; tail -5 $f.err; exit 1; }
       python3 - "$f" "$name" "$ln" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

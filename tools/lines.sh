@@ -33,9 +33,9 @@ else:
     print(f"{op}_n{n}_w{w}")
 EOF
 )
-  timeout -k 10 300 python3 bench.py $args ${CPU_ARGS:-} > "$OUT/${name}_noprof.json" 2> "$OUT/${name}_noprof.err" \
+  timeout -k 10 300 python3 bench.py --full $args ${CPU_ARGS:-} > "$OUT/${name}_noprof.json" 2> "$OUT/${name}_noprof.err" \
     || { echo "FAIL noprof $name"; tail -5 "$OUT/${name}_noprof.err"; exit 1; }
-  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$name" -o run -- python3 bench.py $args --no-cpu-baseline > "$OUT/$name.json" 2> "$OUT/$name.err" \
+  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$name" -o run -- python3 bench.py --full $args --no-cpu-baseline > "$OUT/$name.json" 2> "$OUT/$name.err" \
     || { echo "FAIL trace $name"; tail -5 "$OUT/$name.err"; exit 1; }
   if [ -z "${NO_PMC:-}" ]; then
     timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch_$name" -o run -- python3 bench.py $args --no-cpu-baseline > "$OUT/fetch_$name.log" 2>&1 \

@@ -11,7 +11,7 @@ if [ -n "${TESTS:-}" ]; then
 fi
 for cfg in ${LINES:-}; do
   name=${cfg%%:*}; args=${cfg#*:}
-  timeout -k 10 300 python3 bench.py ${args//,/ } --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "FAIL $name"; tail -5 $O/$name.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full ${args//,/ } --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "FAIL $name"; tail -5 $O/$name.err; exit 1; }
   python3 - "$O/$name.json" "$name" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -5,7 +5,7 @@ SAME command (VERDICT r02 "Next round" #1).
     python tools/roofcheck.py DIR NAME [NAME ...] > DIR/roofcheck.json
 
 DIR holds, per NAME, `NAME.json` (the line printed by `rocprofv3 --kernel-trace
---stats -- python3 bench.py ...`), `trace_NAME/**/run_kernel_stats.csv` (that
+--stats -- python3 bench.py --full ...`), `trace_NAME/**/run_kernel_stats.csv` (that
 run's stats) and optionally `NAME_noprof.json` (the same bench command without
 the profiler, same box).  For the line's dominant kernel it recomputes
     frac_rocprof = alg_bytes_per_launch / rocprof AverageNs / 8000 GB/s

@@ -12,6 +12,6 @@ if [ -z "${SKIP_SUITE:-}" ]; then
 fi
 for cfg in ${LINES:-}; do
   name=${cfg%%:*}; args=${cfg#*:}
-  timeout -k 10 300 python3 bench.py ${args//,/ } --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "FAIL $name"; tail -5 $O/$name.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full ${args//,/ } --no-cpu-baseline > $O/$name.json 2> $O/$name.err || { echo "FAIL $name"; tail -5 $O/$name.err; exit 1; }
   python3 -c "import json,sys; d=json.load(open('$O/$name.json')); print('$name', d['ms_per_step'], d['value'], d['result_ok'], d['roofline']['name'] if d.get('roofline') else None, round(d['roofline']['frac'],3) if d.get('roofline') else None)"
 done
