@@ -82,7 +82,8 @@ constexpr int TP_THREADS = SMJ_TP_THREADS;
 #endif
 // elements a tile-pass thread holds: the stage of a tile is 128 KB of LDS, one
 // tile a CU (16-byte elements: 16-byte tuples in their own layout take half
-// the tile), 64 KB for 32-bit words (two a CU)
+// the tile), 64 KB for 32-bit words (two a CU).  48-bit words keep the tile of
+// 8-byte elements and stage it in 64 KB, a plane at a time (TileStage)
 #ifndef SMJ_TP_STAGE4
 #define SMJ_TP_STAGE4 (64 * 1024)  // the stage of 32-bit words (LayP32): two tiles a CU;
                                    // bench_sort tile pass 0.27 -> 0.19 ms, the step
@@ -103,28 +104,18 @@ constexpr uint32_t tile_elems() {
     return (uint32_t)(TP_THREADS * tp_items<W>());
 }
 static_assert(tile_elems<uint64_t>() <= 65535 + 1, "u16 prefix rows");
-// 48-bit words staged in LDS as two planes (u32 lo, u16 hi: 6 bytes an
-// element) instead of uint64_t: SMJ_TP_STAGE6 bytes of them a tile (0: off).
-// 72 KB (12288 elements) puts two tiles on a CU instead of one 16384-element
-// tile: the tile pass 0.645 -> 0.570 ms, the group pass +0.05 (runs 3/4 as
-// long); the 16-byte join 3.123 -> 3.100 ms, the 8-byte and the Zipf joins
-// within noise, and the group pass becomes the join's longest kernel at 0.82
-// of its credit instead of the scatter at 0.86 (profiles/r06_lab/tile_stage.txt).
-// Off: within the noise between boxes
-#ifndef SMJ_TP_STAGE6
-#define SMJ_TP_STAGE6 0
-#endif
+// The stage of a tile in LDS: kBytes an element, kItems elements a thread.
+// 48-bit words (LayP48) stage their two planes in turn through one 4-byte
+// stage (k_tilepass48 below): 64 KB a 16384-element tile, two tiles a CU.
 template <class Lay>
 struct TileStage {
-    static constexpr bool kSplit = false;
     static constexpr uint32_t kBytes = sizeof(typename Lay::W);
     static constexpr int kItems = tp_items<typename Lay::W>();
 };
 template <>
 struct TileStage<LayP48> {
-    static constexpr bool kSplit = SMJ_TP_STAGE6 > 0;
-    static constexpr uint32_t kBytes = kSplit ? 6 : 8;
-    static constexpr int kItems = kSplit ? SMJ_TP_STAGE6 / 6 / TP_THREADS : tp_items<uint64_t>();
+    static constexpr uint32_t kBytes = 4;
+    static constexpr int kItems = tp_items<uint64_t>();
 };
 template <class Lay>
 constexpr uint32_t tile_elems_l() {
@@ -277,8 +268,6 @@ k_tilepass(TilePassArgs A) {
     const RangePlan& P = A.plan;
     const uint32_t nb2 = A.nb2;
     W* stage = reinterpret_cast<W*>(lds_raw);
-    uint32_t* stage_lo = reinterpret_cast<uint32_t*>(lds_raw);        // kSplit
-    uint16_t* stage_hi = reinterpret_cast<uint16_t*>(lds_raw + TSZ * 4);
     uint32_t* hist = reinterpret_cast<uint32_t*>(lds_raw + ((TSZ * TS::kBytes + 15) & ~15u));
     uint32_t* scr = hist + nb2;
 
@@ -352,22 +341,219 @@ k_tilepass(TilePassArgs A) {
         uint32_t i = j * TP_THREADS + threadIdx.x;
         if (i < len) {
             uint32_t pos = atomicAdd(&hist[dg[j]], 1u);
-            if constexpr (TS::kSplit) {
-                stage_lo[pos] = (uint32_t)v[j];
-                stage_hi[pos] = (uint16_t)(v[j] >> 32);
-            } else {
-                stage[pos] = v[j];
-            }
+            stage[pos] = v[j];
         }
     }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < TP_ITEMS; j++) {
         uint32_t i = j * TP_THREADS + threadIdx.x;
-        if constexpr (TS::kSplit) {
-            if (i < len) st_w(tmp + off + i, (W)stage_lo[i] | ((W)stage_hi[i] << 32));
-        } else {
-            if (i < len) st_w(tmp + off + i, stage[i]);
+        if (i < len) st_w(tmp + off + i, stage[i]);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// The tile pass of 48-bit words (LayP48 in; LayP48 or LayP40 out) with the
+// two planes staged in turn through the same LDS: the elements are ranked
+// once, the lo plane (uint32) is permuted through a 4-byte stage and stored,
+// then the second plane (LayP48: the uint16 hi plane, LayP40: its low byte)
+// goes through the same memory.  A 16384-element tile then needs 64 KB
+// instead of the 128 KB of 8-byte words, so two workgroups share a CU and one
+// tile's loads and stores fly under the other's LDS phases, for two more
+// barriers a tile.  With two 1024-thread workgroups a SIMD holds 8 waves of 64
+// VGPRs: the ranks and the hi plane are held as uint16 pairs and the digits
+// are recomputed in the rank phase instead of held.
+//
+// The second plane is staged at its global byte offset modulo 4, so a dword
+// of the stage is a dword of the plane and leaves with one store.  A tile
+// starts at any element (segment tables, exact shard regions): the dwords at
+// its two ends that it shares with a neighbour tile (of another workgroup)
+// are written as single elements, never as a whole.
+template <class LayO>
+struct Plane2;
+template <>
+struct Plane2<LayP48> {
+    typedef uint16_t T;
+};
+template <>
+struct Plane2<LayP40> {
+    typedef uint8_t T;
+};
+__device__ __forceinline__ void st_plane(G32 p, uint32_t v) {
+#if SMJ_NT_STORES
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+__device__ __forceinline__ void st_plane(G16 p, uint16_t v) {
+#if SMJ_NT_STORES
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+__device__ __forceinline__ void st_plane(G8 p, uint8_t v) {
+#if SMJ_NT_STORES
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+
+// resident workgroups a CU the kernel is built for (launch bounds: waves a SIMD)
+constexpr int TP48_WG_PER_CU = 2;
+
+template <class LayO>
+__global__ void __launch_bounds__(TP_THREADS, TP48_WG_PER_CU * TP_THREADS / 256)
+k_tilepass48(TilePassArgs A) {
+    typedef LayP48 Lay;
+    typedef typename Plane2<LayO>::T HT;
+    constexpr int TP_ITEMS = TileStage<Lay>::kItems;
+    constexpr uint32_t TSZ = tile_elems_l<Lay>();
+    static_assert(TP_ITEMS % 2 == 0, "uint16 pairs");
+    static_assert(TileStage<Lay>::kBytes == 4 && (TSZ + 4) * sizeof(HT) <= TSZ * 4, "one stage");
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    if (A.pack_bad && *A.pack_bad) return;
+    const RangePlan& P = A.plan;
+    const uint32_t nb2 = A.nb2;
+    uint32_t* stage_lo = reinterpret_cast<uint32_t*>(lds_raw);
+    HT* stage_hi = reinterpret_cast<HT*>(lds_raw);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(lds_raw + ((TSZ * 4 + 15) & ~15u));
+    uint32_t* scr = hist + nb2;
+
+    const int r = blockIdx.x < A.nt[0] ? 0 : 1;
+    const uint32_t t = A.t0[r] + (r ? blockIdx.x - A.nt[0] : blockIdx.x);
+    if (A.ntiles[r] && t >= *A.ntiles[r]) return;
+    const TileTable& tt = A.tt[r];
+    const uint64_t off = tt.off[t];
+    const uint32_t len = tt.len[t];
+    const uint32_t b = tt.bucket[t];
+    const Lay::CView part = Lay::cview(A.part[r], A.pstride[r]) + off;
+    const typename LayO::View tmp =
+        LayO::view(A.tmp[r], std::is_same<Lay, LayO>::value ? A.pstride[r] : A.ostride[r]) + off;
+
+    for (uint32_t d = threadIdx.x; d < nb2; d += TP_THREADS) hist[d] = 0;
+    uint32_t lo[TP_ITEMS];
+    uint32_t hp[TP_ITEMS / 2];  // the hi plane, elements 2k and 2k + 1 of the thread
+    uint32_t rk[TP_ITEMS / 2];  // their ranks in the grouped tile
+#pragma unroll
+    for (int k = 0; k < TP_ITEMS / 2; k++) {
+        uint32_t h[2] = {0, 0};
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const int j = 2 * k + e;
+            const uint32_t i = j * TP_THREADS + threadIdx.x;
+            lo[j] = 0;
+            if (i < len) {
+                // uniform base + thread offset: one address register
+                lo[j] = (part.lo + j * TP_THREADS)[threadIdx.x];
+                h[e] = (part.hi + j * TP_THREADS)[threadIdx.x];
+            }
+        }
+        hp[k] = h[0] | (h[1] << 16);
+    }
+    auto word = [&](int j) -> uint64_t {
+        const uint32_t h = (j & 1) ? hp[j >> 1] >> 16 : hp[j >> 1] & 0xffffu;
+        return (uint64_t)lo[j] | ((uint64_t)h << 32);
+    };
+    __syncthreads();
+    // keys outside the plan range (clamped by plan_rel) only sit in the first
+    // and the last bucket: every other tile takes the 32-bit digit
+    const bool fast = A.d2_fast && b != 0 && b != (1u << P.D1) - 1;
+    const uint32_t base_lo = (uint32_t)P.base, mask = nb2 - 1;
+    if (fast) {
+#pragma unroll
+        for (int j = 0; j < TP_ITEMS; j++) {
+            const uint32_t i = j * TP_THREADS + threadIdx.x;
+            if (i < len) atomicAdd(&hist[Lay::digit_fast(word(j), base_lo, P.s1, P.s2, mask)], 1u);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < TP_ITEMS; j++) {
+            const uint32_t i = j * TP_THREADS + threadIdx.x;
+            if (i < len) atomicAdd(&hist[plan_d2(P, Lay::rel(P, word(j), b), b)], 1u);
+        }
+    }
+    __syncthreads();
+    // exclusive scan of the nb2 bins (contiguous range per thread)
+    const uint32_t per = (nb2 + TP_THREADS - 1) / TP_THREADS;
+    const uint32_t d0 = threadIdx.x * per;
+    uint32_t loc = 0;
+    for (uint32_t k = 0; k < per; k++)
+        if (d0 + k < nb2) loc += hist[d0 + k];
+    uint32_t tot;
+    uint32_t ex = block_exclusive_scan(loc, scr, &tot);
+    uint16_t* pref = tt.pref + (uint64_t)t * (nb2 + 1);
+    for (uint32_t k = 0; k < per; k++) {
+        uint32_t d = d0 + k;
+        if (d < nb2) {
+            uint32_t c = hist[d];
+            hist[d] = ex;
+            pref[d] = (uint16_t)ex;
+            ex += c;
+        }
+    }
+    if (threadIdx.x == 0) pref[nb2] = (uint16_t)len;
+    __syncthreads();
+    // ranks (pos < len <= TSZ <= 65536: a uint16 each), the lo plane staged
+#pragma unroll
+    for (int k = 0; k < TP_ITEMS / 2; k++) {
+        uint32_t p[2] = {0, 0};
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const int j = 2 * k + e;
+            const uint32_t i = j * TP_THREADS + threadIdx.x;
+            if (i < len) {
+                const uint64_t w = word(j);
+                const uint32_t d = fast ? Lay::digit_fast(w, base_lo, P.s1, P.s2, mask)
+                                        : plan_d2(P, Lay::rel(P, w, b), b);
+                p[e] = atomicAdd(&hist[d], 1u);
+                stage_lo[p[e]] = lo[j];
+            }
+        }
+        rk[k] = p[0] | (p[1] << 16);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < TP_ITEMS; j++) {
+        const uint32_t i = j * TP_THREADS + threadIdx.x;
+        if (i < len) st_plane(tmp.lo + j * TP_THREADS + threadIdx.x, stage_lo[i]);
+    }
+    __syncthreads();  // the lo plane is read out: the stage is free
+    // the second plane, element i at stage index pad + i: pad = the elements
+    // between the dword boundary below the tile's first element and it
+    constexpr uint32_t EPD = 4 / sizeof(HT);  // elements a dword
+    const uint32_t pad = (uint32_t)(((uintptr_t)tmp.hi & 3u) / sizeof(HT));
+#pragma unroll
+    for (int j = 0; j < TP_ITEMS; j++) {
+        const uint32_t i = j * TP_THREADS + threadIdx.x;
+        if (i < len) {
+            const uint32_t pos = (j & 1) ? rk[j >> 1] >> 16 : rk[j >> 1] & 0xffffu;
+            const uint32_t h = (j & 1) ? hp[j >> 1] >> 16 : hp[j >> 1];
+            stage_hi[pad + pos] = (HT)h;
+        }
+    }
+    __syncthreads();
+    const uint32_t end = pad + len;               // stage indices [pad, end)
+    const uint32_t nq = (end + EPD - 1) / EPD;    // dwords they touch
+    const uint32_t* stage_q = reinterpret_cast<const uint32_t*>(lds_raw);
+    const G32 out_q = (G32)(tmp.hi - pad);        // dword-aligned
+    // TSZ / EPD whole dwords at most, plus one when the tile straddles
+    constexpr int NQ = (int)((TSZ / EPD + TP_THREADS - 1) / TP_THREADS) + 1;
+#pragma unroll
+    for (int j = 0; j < NQ; j++) {
+        const uint32_t q = j * TP_THREADS + threadIdx.x;
+        if (q < nq) {
+            const uint32_t e0 = q * EPD;
+            if (e0 >= pad && e0 + EPD <= end) {
+                st_plane(out_q + j * TP_THREADS + threadIdx.x, stage_q[q]);
+            } else {
+                // a dword shared with the neighbour tile: this tile's elements only
+#pragma unroll
+                for (uint32_t e = e0; e < e0 + EPD; e++)
+                    if (e >= pad && e < end) st_plane(tmp.hi + (e - pad), stage_hi[e]);
+            }
         }
     }
 }
@@ -2277,7 +2463,10 @@ static void launch_tilepass(const TilePassArgs& T, size_t lds, hipStream_t st) {
     // words (8-byte elements, two loads and two stores each for the 48-bit
     // planes) 0.65 -> 0.68-0.71 ms, the prefetch and the stores together
     // saturating the 63 outstanding memory operations; 32-bit words spill
-    if (SMJ_TP_PERSIST && sizeof(typename Lay::W) >= 12) {
+    if constexpr (std::is_same<Lay, LayP48>::value) {
+        // 48-bit words: the planes staged in turn, two workgroups a CU
+        hipLaunchKernelGGL((k_tilepass48<LayO>), dim3(nblk), dim3(TP_THREADS), lds, st, T);
+    } else if (SMJ_TP_PERSIST && sizeof(typename Lay::W) >= 12) {
         hipLaunchKernelGGL((k_tilepass_p<Lay, LayO>), dim3(nblk < 256 ? nblk : 256),
                            dim3(TP_THREADS), lds, st, T);
     } else {
@@ -2285,11 +2474,29 @@ static void launch_tilepass(const TilePassArgs& T, size_t lds, hipStream_t st) {
     }
 }
 
+// dynamic LDS a tile-pass workgroup asks for: the stage, the nb2 digit
+// counters and the scan's scratch (TP_THREADS / 64 + 1 words)
+template <class Lay>
+static size_t tilepass_lds(uint32_t nb2) {
+    return (((size_t)tile_elems_l<Lay>() * TileStage<Lay>::kBytes + 15) & ~(size_t)15) +
+           (size_t)nb2 * 4 + 128;
+}
+
+// the tile-pass kernels a layout pair takes: their dynamic LDS limit
+template <class Lay, class LayO>
+static void set_tilepass_attrs() {
+    if constexpr (std::is_same<Lay, LayP48>::value) {
+        set_lds_attr((const void*)k_tilepass48<LayO>, 160 * 1024);
+    } else {
+        set_lds_attr((const void*)k_tilepass<Lay, LayO>, 160 * 1024);
+        set_lds_attr((const void*)k_tilepass_p<Lay, LayO>, 160 * 1024);
+    }
+}
+
 // dynamic LDS limits of the tile and group passes (per layout)
 template <class Lay>
 static void set_pass_attrs() {
-    set_lds_attr((const void*)k_tilepass<Lay>, 160 * 1024);
-    set_lds_attr((const void*)k_tilepass_p<Lay>, 160 * 1024);
+    if constexpr (!std::is_same<Lay, LayP40>::value) set_tilepass_attrs<Lay, Lay>();
     // several workgroups per CU (launch bounds): ask for what one needs
     const void* gs[4] = {(const void*)k_groupsort<Lay, 2, false>,
                          (const void*)k_groupsort<Lay, 4, false>,
@@ -2368,10 +2575,7 @@ static bool bucket_sort_nosync(Workspace* ws, const BucketSortArgs& a, hipStream
     set_pass_attrs<Lay>();
     set_pass_attrs<LayG>();
     constexpr bool p40 = !std::is_same<Lay, LayG>::value;
-    if (p40) {
-        set_lds_attr((const void*)k_tilepass<Lay, LayG>, 160 * 1024);
-        set_lds_attr((const void*)k_tilepass_p<Lay, LayG>, 160 * 1024);
-    }
+    if (p40) set_tilepass_attrs<Lay, LayG>();
     const uint32_t nb = a.nbuckets;
     const int nrel = a.nrel;
     const uint32_t nb2 = 1u << a.host_plan->D2;
@@ -2476,9 +2680,7 @@ static bool bucket_sort_nosync(Workspace* ws, const BucketSortArgs& a, hipStream
     if (ns) {
         {
             TraceScope ts(ws, "k_tilepass", st);
-            const size_t tp_lds =
-                (((size_t)tsz * TileStage<Lay>::kBytes + 15) & ~(size_t)15) + nb2 * 4 + 64;
-            launch_tilepass<Lay, LayG>(T, tp_lds, st);
+            launch_tilepass<Lay, LayG>(T, tilepass_lds<Lay>(nb2), st);
         }
         const uint32_t ubs[2] = {T.nt[0], T.nt[1]};
         uint32_t* nts[2] = {ntiles[sel[0]], ntiles[sel[ns > 1 ? 1 : 0]]};
@@ -2532,6 +2734,27 @@ static bool bucket_sort_nosync(Workspace* ws, const BucketSortArgs& a, hipStream
     skew_path<LayG>(ws, G, ovf, no, hdst, nb, st);
     SMJ_CHECK(hipGetLastError());
     return true;
+}
+
+// smj_tilepass_occupancy: workgroups of a layout's tile-pass kernel the
+// runtime places on one CU at the launch's dynamic LDS size
+template <class K>
+static int tilepass_blocks(K kernel, size_t lds) {
+    set_lds_attr((const void*)kernel, 160 * 1024);
+    int n = 0;
+    SMJ_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, TP_THREADS, lds));
+    return n;
+}
+int tilepass_occupancy(bool p32, uint32_t d2) {
+    if (d2 > kMaxD2) return -1;
+    const uint32_t nb2 = 1u << d2;
+    if (p32) return tilepass_blocks(k_tilepass<LayP32, LayP32>, tilepass_lds<LayP32>(nb2));
+    // as bucket_sort: 16-byte tuples write LayP40 where the plan allows it
+    RangePlan P{};
+    P.D2 = d2;
+    if (SMJ_P40 && sizeof(Tup) == 16 && LayP40::holds(P))
+        return tilepass_blocks(k_tilepass48<LayP40>, tilepass_lds<LayP48>(nb2));
+    return tilepass_blocks(k_tilepass48<LayP48>, tilepass_lds<LayP48>(nb2));
 }
 
 bool bucket_sort(Workspace* ws, const BucketSortArgs& a, hipStream_t st) {

@@ -1765,6 +1765,11 @@ int smj_workspace_last_layout(smj_workspace* ws) {
     return ((Workspace*)(ws ? ws : smj_context_workspace()))->last_layout;
 }
 
+int smj_tilepass_occupancy(int layout, uint32_t d2_bits) {
+    if (layout != SMJ_LAYOUT_USED_P48 && layout != SMJ_LAYOUT_USED_P32) return -1;
+    return tilepass_occupancy(layout == SMJ_LAYOUT_USED_P32, d2_bits);
+}
+
 void smj_dev_partition(smj_workspace* ws, const tuple_t* in, uint64_t n,
                        tuple_t* out, uint32_t nbits, uint32_t shiftbits,
                        int padded, int64_t* hist_out, int64_t* off_out,

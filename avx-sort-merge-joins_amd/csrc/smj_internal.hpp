@@ -401,6 +401,9 @@ struct BucketSortArgs {
 // Returns false (and does nothing) when a->part_flag reports an overflowed
 // sampled partition: the caller repeats the exact partition.
 bool bucket_sort(Workspace* ws, const BucketSortArgs& a, hipStream_t st);
+// smj_tilepass_occupancy (smj.h) of the 48-bit planes' kernel or (p32) the
+// 32-bit words'
+int tilepass_occupancy(bool p32, uint32_t d2);
 
 // plan selection from a device sample (writes plan_dev)
 // (D2 is the size-preferred level-2 width, D2cap the widest the plan may use

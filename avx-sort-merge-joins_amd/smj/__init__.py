@@ -69,7 +69,7 @@ DEVICE_SYMBOLS = [
     "smj_mgpu_comm_init", "smj_mgpu_rank_join", "smj_mgpu_comm_destroy", "smj_mgpu_rank_sorted",
     "smj_mgpu_comm_workspace", "smj_workspace_last_layout", "smj_mgpu_join_slices",
     "smj_mgpu_last_stats", "smj_mgpu_last_sorted", "smj_mgpu_group_workspace",
-    "smj_dev_partition_range_shards",
+    "smj_dev_partition_range_shards", "smj_tilepass_occupancy",
 ]
 
 
@@ -304,6 +304,7 @@ class Library:
             "smj_inregister_sort_keyval32": (None, [_P, _P, _U64]),
             "smj_workspace_set_layouts": (None, [_P, _U32]),
             "smj_workspace_last_layout": (C.c_int, [_P]),
+            "smj_tilepass_occupancy": (C.c_int, [C.c_int, _U32]),
             "smj_trace_enable": (None, [_P, C.c_int]),
             "smj_trace_reset": (None, [_P]),
             "smj_trace_only": (None, [_P, C.c_char_p]),
@@ -620,6 +621,12 @@ class Library:
             return "unknown"
         k = f(None if api else self.ws)
         return LAYOUTS_USED[k] if k >= 0 else "none"
+
+    def tilepass_occupancy(self, layout: str = "p48", d2_bits: int = 10) -> int:
+        """smj_tilepass_occupancy: workgroups of the tile-pass kernel of
+        intermediate layout `layout` ("p48" or "p32") that share a compute
+        unit at 2^d2_bits level-2 digits; -1 where it does not apply."""
+        return int(self.lib.smj_tilepass_occupancy(LAYOUTS_USED.index(layout), d2_bits))
 
     @staticmethod
     def stream_ptr():

@@ -554,6 +554,15 @@ void smj_workspace_set_layouts(smj_workspace * ws, uint32_t off);
 #define SMJ_LAYOUT_USED_P32    3
 #define SMJ_LAYOUT_USED_P96    4
 int smj_workspace_last_layout(smj_workspace * ws);
+/* Workgroups of the tile-pass kernel that intermediate layout `layout`
+ * (SMJ_LAYOUT_USED_P48 or _P32) takes which the runtime places on one compute
+ * unit (hipOccupancyMaxActiveBlocksPerMultiprocessor) at the dynamic LDS size
+ * of a launch with 2^d2_bits level-2 digits.  The 48-bit planes are staged in
+ * turn so that two 16384-element tiles share a compute unit:
+ * this is the guard against losing the second one to a register or LDS
+ * budget.  -1 for a layout without such a kernel or d2_bits beyond the
+ * plan's limit. */
+int smj_tilepass_occupancy(int layout, uint32_t d2_bits);
 
 /* Stable radix partition, the device form of partition_relation*.
  * padded != 0 -> partition_relation_optimized layout.
