@@ -1812,6 +1812,21 @@ uint64_t smj_dev_materialize(smj_workspace* ws, const tuple_t* sortedR, uint64_t
                        nS, (Tup*)out, out_cap, (hipStream_t)stream);
 }
 
+uint64_t smj_dev_join_pairs(smj_workspace* ws, const tuple_t* sortedR, uint64_t nR,
+                            const tuple_t* sortedS, uint64_t nS, value_t* r_payload_out,
+                            value_t* s_payload_out, intkey_t* key_out, uint64_t out_cap,
+                            smj_stream_t stream) {
+    return join_pairs((Workspace*)ws, (const Tup*)sortedR, nR, (const Tup*)sortedS, nS,
+                      r_payload_out, s_payload_out, key_out, out_cap, (hipStream_t)stream);
+}
+
+uint64_t smj_dev_semi_join(smj_workspace* ws, const tuple_t* sortedR, uint64_t nR,
+                           const tuple_t* sortedS, uint64_t nS, tuple_t* out,
+                           uint64_t out_cap, int anti, smj_stream_t stream) {
+    return semi_join((Workspace*)ws, (const Tup*)sortedR, nR, (const Tup*)sortedS, nS,
+                     (Tup*)out, out_cap, anti, (hipStream_t)stream);
+}
+
 void smj_dev_join(smj_workspace* ws, const tuple_t* R, uint64_t nR,
                   const tuple_t* S, uint64_t nS, tuple_t* sortedR,
                   tuple_t* sortedS, uint32_t fanout_bits, int64_t key_min,

@@ -437,6 +437,16 @@ void multiway_merge_tree(Workspace* ws, const Tup* const* runs_host,
 // (synchronises `st` once, for the launch size of the write pass).
 uint64_t materialize(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S,
                      uint64_t nS, Tup* out, uint64_t out_cap, hipStream_t st);
+// The join index: for output position q of materialize(), the payloads of
+// the matching R and S tuples (and the key, unless key_out is null) as
+// columns of the ABI's value_t / intkey_t.  The same capacity and
+// synchronisation rules.
+uint64_t join_pairs(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
+                    void* r_out, void* s_out, void* key_out, uint64_t out_cap,
+                    hipStream_t st);
+// The S tuples whose key occurs in R (anti: does not occur), in sorted order.
+uint64_t semi_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
+                   Tup* out, uint64_t out_cap, int anti, hipStream_t st);
 
 // ---- datagen.hip
 void gen_pk(Tup* out, uint64_t n, uint64_t first, uint64_t total,

@@ -70,6 +70,7 @@ DEVICE_SYMBOLS = [
     "smj_mgpu_comm_workspace", "smj_workspace_last_layout", "smj_mgpu_join_slices",
     "smj_mgpu_last_stats", "smj_mgpu_last_sorted", "smj_mgpu_group_workspace",
     "smj_dev_partition_range_shards", "smj_tilepass_occupancy",
+    "smj_dev_join_pairs", "smj_dev_semi_join",
 ]
 
 
@@ -278,6 +279,8 @@ class Library:
             "smj_sampled_capacity": (_U64, [_U64, _U32]),
             "smj_sampled_shards": (_U32, []),
             "smj_dev_materialize": (_U64, [_P, _P, _U64, _P, _U64, _P, _U64, _P]),
+            "smj_dev_join_pairs": (_U64, [_P, _P, _U64, _P, _U64, _P, _P, _P, _U64, _P]),
+            "smj_dev_semi_join": (_U64, [_P, _P, _U64, _P, _U64, _P, _U64, C.c_int, _P]),
             "smj_selfcheck_lds_order": (_U64, [_P, _P]),
             "smj_context_workspace": (_P, []),
             "smj_dev_gen_nonunique": (None, [_P, _P, _U64, _U64, _U64, _I64, _U32, _U64, _P]),
@@ -725,6 +728,56 @@ class Library:
         return int(self.lib.smj_dev_materialize(
             self.ws, sortedR.data_ptr(), sortedR.shape[0], sortedS.data_ptr(),
             sortedS.shape[0], out.data_ptr() if cap else None, cap, self.stream_ptr()))
+
+    def _column(self, t, cap, what):
+        dt = torch.int32 if self.width == 8 else torch.int64
+        assert t.dim() == 1 and t.dtype == dt and t.is_contiguous() and t.is_cuda, what
+        assert t.shape[0] >= cap, f"{what} holds fewer than the {cap} of r_out"
+        return t.data_ptr() if cap else None
+
+    def dev_join_pairs(self, sortedR, sortedS, r_out=None, s_out=None, key_out=None):
+        """The join index (smj_dev_join_pairs): for the first len(r_out)
+        matches, in dev_materialize's order, the payloads of the matching R
+        and S tuples (and the keys, with key_out) into 1-D device tensors of
+        the payload dtype; returns the total.  No outputs: count only."""
+        cap = 0 if r_out is None else r_out.shape[0]
+        assert (s_out is None) == (r_out is None), "r_out and s_out go together"
+        assert r_out is not None or key_out is None, "key_out needs r_out and s_out"
+        rp = self._column(r_out, cap, "r_out") if r_out is not None else None
+        sp = self._column(s_out, cap, "s_out") if s_out is not None else None
+        kp = self._column(key_out, cap, "key_out") if key_out is not None else None
+        return int(self.lib.smj_dev_join_pairs(
+            self.ws, sortedR.data_ptr(), sortedR.shape[0], sortedS.data_ptr(),
+            sortedS.shape[0], rp, sp, kp, cap, self.stream_ptr()))
+
+    def dev_semi_join(self, sortedR, sortedS, out=None, anti=False):
+        """Semi join (smj_dev_semi_join): the first len(out) tuples of sortedS
+        whose key occurs in sortedR (anti: does not occur), in sorted order;
+        returns their total.  out=None: count only."""
+        cap = 0 if out is None else out.shape[0]
+        return int(self.lib.smj_dev_semi_join(
+            self.ws, sortedR.data_ptr(), sortedR.shape[0], sortedS.data_ptr(),
+            sortedS.shape[0], out.data_ptr() if cap else None, cap, int(bool(anti)),
+            self.stream_ptr()))
+
+    def join_index(self, R, S, key_range=None, with_keys=False):
+        """The join index of two unsorted device relations in one call: sorts
+        and joins them (dev_join) into temporaries, takes the match count and
+        returns exactly sized 1-D tensors (r_payloads, s_payloads[, keys]) on
+        the current stream, in dev_join_pairs' order.  key_range: an optional
+        (key_min, key_max) hint of the keys present, as in dev_join."""
+        dt = torch.int32 if self.width == 8 else torch.int64
+        sR, sS = self.empty(R.shape[0]), self.empty(S.shape[0])
+        count = torch.zeros(1, dtype=torch.int64, device=R.device)
+        kmin, kmax = key_range if key_range is not None else (1, 0)
+        self.dev_join(R, S, sR, sS, count, 10, kmin, kmax)
+        total = int(count.item())
+        cols = [torch.empty(total, dtype=dt, device=R.device)
+                for _ in range(3 if with_keys else 2)]
+        if total:
+            got = self.dev_join_pairs(sR, sS, *cols)
+            assert got == total, (got, total)
+        return tuple(cols)
 
     def dev_join(self, R, S, sortedR, sortedS, count, fanout_bits=10,
                  key_min=1, key_max=0):

@@ -606,6 +606,33 @@ uint64_t smj_dev_materialize(smj_workspace * ws, const tuple_t * sortedR,
                              uint64_t nR, const tuple_t * sortedS, uint64_t nS,
                              tuple_t * out, uint64_t out_cap, smj_stream_t stream);
 
+/* The join index of two sorted relations: which rows matched.  For output
+ * position q, in exactly the order smj_dev_materialize emits -- keys
+ * ascending; per key R-major: for each R tuple of the key's run in sorted
+ * order, the whole S run in sorted order -- r_payload_out[q] is the payload
+ * of the matching R tuple, s_payload_out[q] that of the matching S tuple
+ * (the payload column of smj_dev_materialize's output), and key_out[q] the
+ * key, unless key_out is NULL.  With row ids as payloads these are the
+ * columns a caller gathers its other columns with.  Three separate device
+ * columns of out_cap elements each: the first min(total, out_cap) positions
+ * are written, the rest are left alone, and the total number of matches is
+ * returned (it may exceed 2^32); out_cap = 0 only counts.  Synchronises
+ * `stream` once. */
+uint64_t smj_dev_join_pairs(smj_workspace * ws, const tuple_t * sortedR, uint64_t nR,
+                            const tuple_t * sortedS, uint64_t nS, value_t * r_payload_out,
+                            value_t * s_payload_out, intkey_t * key_out /* may be NULL */,
+                            uint64_t out_cap, smj_stream_t stream);
+
+/* Semi join (anti = 0): the tuples of sortedS whose key occurs in sortedR,
+ * in sorted order; anti join (anti != 0): those whose key does not.  The
+ * same filter on the R side is the call with the relations swapped.  Writes
+ * the first min(total, out_cap) tuples to `out` (device) and returns the
+ * total; out_cap = 0 only counts.  nR = 0 gives nothing (semi) or all of S
+ * (anti).  Synchronises `stream` once (not at all when nR or nS is 0). */
+uint64_t smj_dev_semi_join(smj_workspace * ws, const tuple_t * sortedR, uint64_t nR,
+                           const tuple_t * sortedS, uint64_t nS, tuple_t * out,
+                           uint64_t out_cap, int anti, smj_stream_t stream);
+
 /* The m-way join on one device.  R and S are left untouched; sortedR/sortedS
  * (n tuples each) receive the fully sorted relations; the match count is
  * written to *count_dev.  key_min <= key_max is an optional hint of the key
