@@ -1827,6 +1827,23 @@ uint64_t smj_dev_semi_join(smj_workspace* ws, const tuple_t* sortedR, uint64_t n
                      (Tup*)out, out_cap, anti, (hipStream_t)stream);
 }
 
+uint64_t smj_dev_band_join(smj_workspace* ws, const tuple_t* sortedR, uint64_t nR,
+                           const tuple_t* sortedS, uint64_t nS, int64_t lo, int64_t hi,
+                           value_t* r_payload_out, value_t* s_payload_out,
+                           intkey_t* r_key_out, intkey_t* s_key_out, uint64_t out_cap,
+                           smj_stream_t stream) {
+    return band_join((Workspace*)ws, (const Tup*)sortedR, nR, (const Tup*)sortedS, nS, lo, hi,
+                     r_payload_out, s_payload_out, r_key_out, s_key_out, out_cap,
+                     (hipStream_t)stream);
+}
+
+void smj_dev_band_join_count(smj_workspace* ws, const tuple_t* sortedR, uint64_t nR,
+                             const tuple_t* sortedS, uint64_t nS, int64_t lo, int64_t hi,
+                             unsigned long long* count_dev, smj_stream_t stream) {
+    band_join_count((Workspace*)ws, (const Tup*)sortedR, nR, (const Tup*)sortedS, nS, lo, hi,
+                    count_dev, (hipStream_t)stream);
+}
+
 void smj_dev_join(smj_workspace* ws, const tuple_t* R, uint64_t nR,
                   const tuple_t* S, uint64_t nS, tuple_t* sortedR,
                   tuple_t* sortedS, uint32_t fanout_bits, int64_t key_min,

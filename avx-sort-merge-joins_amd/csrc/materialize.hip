@@ -35,45 +35,13 @@
 //          the ordered copy of the bitmap tiles -- no R access, no search.
 #include "smj_common.hpp"
 #include "smj_internal.hpp"
+#include "mat_common.hpp"
 
 #include <type_traits>
 
 namespace smj {
 
-constexpr int MT_THREADS = 256;
-// small tiles keep the LDS per workgroup at 18 KB (8 workgroups per CU), so
-// the staging loads of some workgroups overlap the searches of others
-// (16 B, 128M x 128M, before the bitmap path: 2048-element tiles 6.6 ms,
-// 1024: 4.6 ms, 512: 4.2 ms; with it: 1024: 2.9 ms, 512: 2.4 ms, 256: 3.7 ms
-// -- more, smaller tiles lose to the per-tile searches and launch width)
-constexpr int MT_IPT = 2;
-constexpr uint32_t MT_TILE = MT_THREADS * MT_IPT;  // S elements per tile
-constexpr uint32_t MT_RWIN = 2 * MT_TILE;          // R keys staged in LDS
-constexpr uint64_t kMatPiece = 8192;                // outputs per work item
-
 enum MatMode { MAT_TUPLES = 0, MAT_PAIRS = 1, MAT_SEMI = 2 };
-
-#ifdef KEY_8B
-typedef int64_t MatVal;  // value_t and intkey_t of the C ABI
-#else
-typedef int32_t MatVal;
-#endif
-
-__device__ __forceinline__ MatVal mat_payload(const Tup* p) {
-#ifdef KEY_8B
-    return p->payload;
-#else
-    return (MatVal)(uint32_t)*p;
-#endif
-}
-
-__device__ __forceinline__ void st_val(MatVal* p, MatVal v) {
-#if SMJ_NT_STORES
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
 
 // the output columns of the pair mode (key may be null)
 struct PairCols {
@@ -88,39 +56,6 @@ __device__ __forceinline__ void st_pair(const PairCols& o, uint64_t q, MatVal rp
     st_val(o.s + q, mat_payload(&s));
     if (o.key) st_val(o.key + q, (MatVal)tup_key(s));
 }
-
-// first index of [lo, hi) whose key is >= k (UPPER: > k); K(i) = key i
-template <bool UPPER, class K>
-__device__ __forceinline__ uint64_t key_search(K key, uint64_t lo, uint64_t hi,
-                                               int64_t k) {
-    while (lo < hi) {
-        const uint64_t m = (lo + hi) >> 1;
-        const int64_t x = key(m);
-        if (UPPER ? x <= k : x < k) lo = m + 1; else hi = m;
-    }
-    return lo;
-}
-
-// the same answer, galloping forward from lo (consecutive keys of a tile sit
-// close together in R)
-template <bool UPPER, class K>
-__device__ __forceinline__ uint64_t key_gallop(K key, uint64_t lo, uint64_t hi,
-                                               int64_t k) {
-    uint64_t step = 1;
-    while (true) {
-        const uint64_t e = lo + step - 1;
-        if (e >= hi) return key_search<UPPER>(key, lo, hi, k);
-        const int64_t x = key(e);
-        if (!(UPPER ? x <= k : x < k)) return key_search<UPPER>(key, lo, e, k);
-        lo = e + 1;
-        step <<= 1;
-    }
-}
-
-struct TupKey {
-    const Tup* a;
-    __device__ __forceinline__ int64_t operator()(uint64_t i) const { return tup_key(a[i]); }
-};
 
 // per tile: R window [lo, hi), S start of the first key run, S end of the last
 __global__ void __launch_bounds__(256)
@@ -225,34 +160,6 @@ __device__ void mat_tile(const Tup* __restrict__ R, const Tup* __restrict__ S,
     } else {
         mat_runs(TupKey{R}, Rlo, Rhi, i0, i1, len, L);
     }
-}
-
-// block-wide exclusive scan of one uint64 per thread
-__device__ __forceinline__ uint64_t block_scan64(uint64_t v, uint64_t* wsum,
-                                                 uint64_t* total) {
-    const int lane = lane_id(), wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint64_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t y = __shfl_up((unsigned long long)x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wid] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t run = 0;
-        for (int w = 0; w < nw; w++) {
-            const uint64_t t = wsum[w];
-            wsum[w] = run;
-            run += t;
-        }
-        wsum[nw] = run;
-    }
-    __syncthreads();
-    const uint64_t res = wsum[wid] + x - v;
-    if (total) *total = wsum[nw];
-    __syncthreads();
-    return res;
 }
 
 // MODE pairs: a bitmap tile also leaves partner[S index] = the offset of the
@@ -387,6 +294,20 @@ k_mat_down(const uint64_t* __restrict__ cnt, uint64_t ntiles,
         base[t] = part[2 * blockIdx.x] + eo;
         ibase[t] = part[2 * blockIdx.x + 1] + ei;
     }
+}
+
+void mat_scan(Workspace* ws, const uint64_t* cnt, uint64_t ntiles, uint64_t* base,
+              uint64_t* ibase, uint64_t* tot, hipStream_t st) {
+    TraceScope ts(ws, "k_mat_scan", st);
+    const uint32_t nb = (uint32_t)((ntiles + MS_BLOCK - 1) / MS_BLOCK);
+    uint64_t* part = (uint64_t*)ws->scratch("mat_part", (size_t)nb * 16);
+    hipLaunchKernelGGL(k_mat_part, dim3(nb), dim3(MS_BLOCK), 0, st, cnt, ntiles, part);
+    SMJ_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_mat_pscan, dim3(1), dim3(MS_BLOCK), 0, st, part, nb, tot);
+    SMJ_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_mat_down, dim3(nb), dim3(MS_BLOCK), 0, st, cnt, ntiles, part, base,
+                       ibase);
+    SMJ_CHECK(hipGetLastError());
 }
 
 // MODE tuples writes `out`; MODE pairs writes the columns `cols` (semi joins
@@ -534,18 +455,7 @@ static uint64_t mat_passes(Workspace* ws, const Tup* R, uint64_t nR, const Tup* 
                            st, R, S, nS, bounds, cnt, bitmap, multi, partner, anti);
         SMJ_CHECK(hipGetLastError());
     }
-    {
-        TraceScope ts(ws, "k_mat_scan", st);
-        const uint32_t nb = (uint32_t)((ntiles + MS_BLOCK - 1) / MS_BLOCK);
-        uint64_t* part = (uint64_t*)ws->scratch("mat_part", (size_t)nb * 16);
-        hipLaunchKernelGGL(k_mat_part, dim3(nb), dim3(MS_BLOCK), 0, st, cnt, ntiles, part);
-        SMJ_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_mat_pscan, dim3(1), dim3(MS_BLOCK), 0, st, part, nb, tot);
-        SMJ_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_mat_down, dim3(nb), dim3(MS_BLOCK), 0, st, cnt, ntiles, part,
-                           base, ibase);
-        SMJ_CHECK(hipGetLastError());
-    }
+    mat_scan(ws, cnt, ntiles, base, ibase, tot, st);
     uint64_t* h = (uint64_t*)ws->host_pinned("mat_tot_h", 16);
     SMJ_CHECK(hipMemcpyAsync(h, tot, 16, hipMemcpyDeviceToHost, st));
     SMJ_CHECK(hipStreamSynchronize(st));

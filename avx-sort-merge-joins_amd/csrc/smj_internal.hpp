@@ -447,6 +447,23 @@ uint64_t join_pairs(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint
 // The S tuples whose key occurs in R (anti: does not occur), in sorted order.
 uint64_t semi_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
                    Tup* out, uint64_t out_cap, int anti, hipStream_t st);
+// The scan between the count pass and the write pass (traced as k_mat_scan):
+// from the output counts of ntiles S tiles, the tiles' output bases and the
+// bases of their work items (pieces of kMatPiece outputs, mat_common.hpp),
+// both exclusive; tot[0..1] = the outputs and the work items in all.
+void mat_scan(Workspace* ws, const uint64_t* cnt, uint64_t ntiles, uint64_t* base,
+              uint64_t* ibase, uint64_t* tot, hipStream_t st);
+
+// ---- bandjoin.hip : band join of sorted R and S (smj.h smj_dev_band_join)
+// Every pair with s.key + lo <= r.key <= s.key + hi, S-major, as columns of
+// the ABI's value_t / intkey_t (the key columns may be null); materialize()'s
+// capacity and synchronisation rules.
+uint64_t band_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
+                   int64_t lo, int64_t hi, void* r_out, void* s_out, void* r_key_out,
+                   void* s_key_out, uint64_t out_cap, hipStream_t st);
+// its count, added to *count_dev (stream-ordered, no synchronisation)
+void band_join_count(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
+                     int64_t lo, int64_t hi, unsigned long long* count_dev, hipStream_t st);
 
 // ---- datagen.hip
 void gen_pk(Tup* out, uint64_t n, uint64_t first, uint64_t total,

@@ -71,6 +71,7 @@ DEVICE_SYMBOLS = [
     "smj_mgpu_last_stats", "smj_mgpu_last_sorted", "smj_mgpu_group_workspace",
     "smj_dev_partition_range_shards", "smj_tilepass_occupancy",
     "smj_dev_join_pairs", "smj_dev_semi_join",
+    "smj_dev_band_join", "smj_dev_band_join_count",
 ]
 
 
@@ -281,6 +282,9 @@ class Library:
             "smj_dev_materialize": (_U64, [_P, _P, _U64, _P, _U64, _P, _U64, _P]),
             "smj_dev_join_pairs": (_U64, [_P, _P, _U64, _P, _U64, _P, _P, _P, _U64, _P]),
             "smj_dev_semi_join": (_U64, [_P, _P, _U64, _P, _U64, _P, _U64, C.c_int, _P]),
+            "smj_dev_band_join": (_U64, [_P, _P, _U64, _P, _U64, _I64, _I64, _P, _P, _P, _P,
+                                         _U64, _P]),
+            "smj_dev_band_join_count": (None, [_P, _P, _U64, _P, _U64, _I64, _I64, _P, _P]),
             "smj_selfcheck_lds_order": (_U64, [_P, _P]),
             "smj_context_workspace": (_P, []),
             "smj_dev_gen_nonunique": (None, [_P, _P, _U64, _U64, _U64, _I64, _U32, _U64, _P]),
@@ -776,6 +780,59 @@ class Library:
                 for _ in range(3 if with_keys else 2)]
         if total:
             got = self.dev_join_pairs(sR, sS, *cols)
+            assert got == total, (got, total)
+        return tuple(cols)
+
+    @staticmethod
+    def _band(lo, hi):
+        lo, hi = int(lo), int(hi)
+        for v in (lo, hi):
+            assert -(1 << 63) <= v < (1 << 63), "lo and hi are int64"
+        return lo, hi
+
+    def dev_band_join(self, sortedR, sortedS, lo, hi, r_out=None, s_out=None,
+                      r_key_out=None, s_key_out=None):
+        """Band join (smj_dev_band_join): the pairs with s.key + lo <= r.key
+        <= s.key + hi, S-major.  For the first len(r_out) of them the payloads
+        of the R and the S tuple (and their keys, with r_key_out / s_key_out)
+        into 1-D device tensors of the payload dtype; returns the total.  No
+        outputs: count only."""
+        lo, hi = self._band(lo, hi)
+        cap = 0 if r_out is None else r_out.shape[0]
+        assert (s_out is None) == (r_out is None), "r_out and s_out go together"
+        assert r_out is not None or (r_key_out is None and s_key_out is None), \
+            "key columns need r_out and s_out"
+        ptrs = [self._column(t, cap, what) if t is not None else None
+                for t, what in ((r_out, "r_out"), (s_out, "s_out"),
+                                (r_key_out, "r_key_out"), (s_key_out, "s_key_out"))]
+        return int(self.lib.smj_dev_band_join(
+            self.ws, sortedR.data_ptr(), sortedR.shape[0], sortedS.data_ptr(),
+            sortedS.shape[0], lo, hi, *ptrs, cap, self.stream_ptr()))
+
+    def dev_band_join_count(self, sortedR, sortedS, lo, hi, count):
+        """smj_dev_band_join_count: the band join's count added to count[0]
+        (int64 device tensor), stream-ordered."""
+        lo, hi = self._band(lo, hi)
+        self.lib.smj_dev_band_join_count(
+            self.ws, sortedR.data_ptr(), sortedR.shape[0], sortedS.data_ptr(),
+            sortedS.shape[0], lo, hi, count.data_ptr(), self.stream_ptr())
+
+    def band_join(self, R, S, lo, hi, with_keys=False):
+        """The band join of two unsorted device relations in one call: sorts
+        both (dev_sort) into temporaries, takes the count and returns exactly
+        sized 1-D tensors (r_payloads, s_payloads[, r_keys, s_keys]) on the
+        current stream, in dev_band_join's order."""
+        dt = torch.int32 if self.width == 8 else torch.int64
+        total = 0
+        if R.shape[0] and S.shape[0]:
+            sR, sS = self.empty(R.shape[0]), self.empty(S.shape[0])
+            self.dev_sort(R, sR)
+            self.dev_sort(S, sS)
+            total = self.dev_band_join(sR, sS, lo, hi)
+        cols = [torch.empty(total, dtype=dt, device=R.device)
+                for _ in range(4 if with_keys else 2)]
+        if total:
+            got = self.dev_band_join(sR, sS, lo, hi, *cols)
             assert got == total, (got, total)
         return tuple(cols)
 

@@ -633,6 +633,43 @@ uint64_t smj_dev_semi_join(smj_workspace * ws, const tuple_t * sortedR, uint64_t
                            const tuple_t * sortedS, uint64_t nS, tuple_t * out,
                            uint64_t out_cap, int anti, smj_stream_t stream);
 
+/* Band join of two sorted relations: every pair (r, s) with
+ * s.key + lo <= r.key <= s.key + hi (the library's own; the join a sort-merge
+ * library offers and a hash join cannot).
+ * Predicate: evaluated without wrap-around.  The 8-byte library computes
+ *   s.key + lo and s.key + hi in int64, so a lo or hi beyond the int32 range
+ *   means "unbounded on that side"; the 16-byte library saturates the sums at
+ *   INT64_MIN and INT64_MAX.  An S tuple whose whole band lies outside int64
+ *   (s.key + lo > INT64_MAX or s.key + hi < INT64_MIN) has no partner.
+ * Empty calls: lo > hi, nR == 0 or nS == 0 return 0, launch nothing and do
+ *   not synchronise.
+ * Order: S-major, by position in the sorted arrays -- for each S tuple in
+ *   sorted order, its partners sortedR[lb .. ub) in sorted order.  This is
+ *   deterministic given the sorted inputs (8-byte tie order included).  It is
+ *   NOT smj_dev_join_pairs' order for lo = hi = 0 when a key repeats on both
+ *   sides (that one is R-major per key); the two coincide when, for every
+ *   key, one side holds it at most once.
+ * Output: position q gets the payloads of its R and S tuple in
+ *   r_payload_out[q] and s_payload_out[q] and their keys in r_key_out[q] and
+ *   s_key_out[q] (each key column may be NULL).  The first
+ *   min(total, out_cap) positions of every non-NULL column are written, the
+ *   rest are left alone, and the total is returned (it may exceed 2^32);
+ *   out_cap = 0 only counts, and the payload columns may then be NULL.
+ *   Synchronises `stream` once. */
+uint64_t smj_dev_band_join(smj_workspace * ws, const tuple_t * sortedR, uint64_t nR,
+                           const tuple_t * sortedS, uint64_t nS, int64_t lo, int64_t hi,
+                           value_t * r_payload_out, value_t * s_payload_out,
+                           intkey_t * r_key_out /* may be NULL */,
+                           intkey_t * s_key_out /* may be NULL */,
+                           uint64_t out_cap, smj_stream_t stream);
+
+/* Its count only, ADDED to *count_dev (device), stream-ordered like
+ * smj_dev_merge_join_count: no host synchronisation (the workspace's tables
+ * grow on a first call).  The same predicate and empty calls. */
+void smj_dev_band_join_count(smj_workspace * ws, const tuple_t * sortedR, uint64_t nR,
+                             const tuple_t * sortedS, uint64_t nS, int64_t lo, int64_t hi,
+                             unsigned long long * count_dev, smj_stream_t stream);
+
 /* The m-way join on one device.  R and S are left untouched; sortedR/sortedS
  * (n tuples each) receive the fully sorted relations; the match count is
  * written to *count_dev.  key_min <= key_max is an optional hint of the key

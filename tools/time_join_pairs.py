@@ -12,8 +12,9 @@ then run round-robin on the sorted relations, each timed with device events
 (every call synchronises its stream once, which the events include), and the
 medians are printed as one JSON line.  --also NAME=DIR names another build
 of the libraries (make BUILD=... LIBOUT=...): its smj_dev_materialize, and
-its smj_dev_join_pairs where it has one, join the round-robin as
-materialize_NAME / join_pairs_NAME, so an older commit's kernels or a variant
+its smj_dev_join_pairs and smj_dev_semi_join where it has them, join the
+round-robin as materialize_NAME / join_pairs_NAME / semi_join_NAME, so an older
+commit's kernels or a variant
 build are timed beside this one's.
 --trace adds the per-kernel times of one more join-pairs call.  --n shrinks
 the relations for a functional check; timings at small n measure overheads.
@@ -110,6 +111,8 @@ def main():
                 calls["materialize_" + tag] = lambda o=o: o.dev_materialize(sR, sS, out)
                 if hasattr(o.lib, "smj_dev_join_pairs"):
                     calls["join_pairs_" + tag] = lambda o=o: o.dev_join_pairs(sR, sS, *cols)
+                if hasattr(o.lib, "smj_dev_semi_join"):
+                    calls["semi_join_" + tag] = lambda o=o: o.dev_semi_join(sR, sS, out)
             for name, fn in calls.items():
                 got = fn()
                 assert got == total, (name, got, total)
