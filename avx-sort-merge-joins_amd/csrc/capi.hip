@@ -603,8 +603,17 @@ static void device_sort(Workspace* ws, const Tup* in, uint64_t n, Tup* out,
     if (n == 0) return;
     const Tup* rels[1] = {in};
     uint64_t ns[1] = {n};
-    Tup* outs[1] = {out};
+    // `out` may be `in` (scalarsort_tuples sorts in place).  An attempt of
+    // device_bucket whose regions overflow still runs its tile and group
+    // passes and writes `out` before it is discarded, and the next attempt
+    // reads `in` again: an output that overlaps the input is sorted into
+    // scratch and copied over the input once the sort has finished.
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out, len = (uintptr_t)n * sizeof(Tup);
+    const bool overlap = a < b + len && b < a + len;
+    Tup* outs[1] = {overlap ? (Tup*)ws->scratch("sort_inplace", n * sizeof(Tup)) : out};
     device_bucket(ws, rels, ns, 1, outs, 0, 1, 0, n, nullptr, st);
+    if (overlap)
+        SMJ_CHECK(hipMemcpyAsync(out, outs[0], n * sizeof(Tup), hipMemcpyDeviceToDevice, st));
 }
 
 static void device_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S,

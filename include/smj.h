@@ -19,6 +19,10 @@
  * addresses/layout) or device memory from hipMalloc (work stays in HBM, no
  * copies).  The smj_dev_* functions are the asynchronous device-resident form
  * used by bench.py: device pointers only, explicit HIP stream, no host sync.
+ * Device pointers: aligned to 8 bytes for 8-byte tuples, to 16 bytes for
+ * 16-byte tuples; nothing more is assumed.  Any tuple-granular slice of a
+ * hipMalloc buffer is therefore a valid relation or output, used in place
+ * (element columns -- value_t, intkey_t, int64 words -- to their element).
  *
  * Order of the sorted output (the parity contract):
  *   8-byte tuples : ascending signed-int64 order of the packed word
@@ -573,7 +577,9 @@ void smj_dev_partition(smj_workspace * ws, const tuple_t * in, uint64_t n,
                        int padded, int64_t * hist_out, int64_t * off_out,
                        smj_stream_t stream);
 
-/* Full sort of n tuples into `out` (may equal `in`). */
+/* Full sort of n tuples into `out`.  `out` may equal or overlap `in`: the
+ * sort then runs into workspace scratch and is copied over the input at the
+ * end (one more pass over n tuples); otherwise `in` is left untouched. */
 void smj_dev_sort(smj_workspace * ws, const tuple_t * in, uint64_t n,
                   tuple_t * out, smj_stream_t stream);
 
@@ -723,8 +729,9 @@ uint32_t smj_glibc_rand(uint32_t seed, uint64_t k);
 
 void smj_dev_synchronize(smj_stream_t stream);
 
-/* Multi-GPU building block: stable partition of a device relation into
- * 2^nbits key ranges of [key_min, key_max] (monotone digits, unpadded), so a
+/* Multi-GPU building block: partition of a device relation into 2^nbits key
+ * ranges of [key_min, key_max] (monotone digits, unpadded, partitions back to
+ * back; the order inside a partition is free: it is sorted afterwards), so a
  * caller can hand contiguous partition ranges to their owner GPU with one
  * all-to-all (bench.py does this over RCCL).  hist_out: device int64[2^nbits]. */
 void smj_dev_partition_range(smj_workspace * ws, const tuple_t * in, uint64_t n,

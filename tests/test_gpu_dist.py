@@ -31,11 +31,20 @@ def _inputs(orc, kind, n):
 @pytest.mark.parametrize("kind", ["pk_fk", "zipf"])
 @pytest.mark.parametrize("packed", [False, True])
 def test_segmented_join_simulated_exchange(libs, oracles, width, world, kind, packed):
-    import torch
-    from smj.dist import DistributedJoin, ceil_log2, owned, plan_shift, used_parts
-    orc, lib = oracles[width], libs[width]
     if packed and width != 16:
         pytest.skip("packed words are the 16-byte layout")
+    segmented_exchange_case(libs[width], oracles[width], world, kind, packed)
+
+
+def segmented_exchange_case(lib, orc, world, kind, packed, off=0):
+    """The simulated exchange and the segmented join of every rank.  off: the
+    element offset of every partition input and output and of the receive
+    buffers (the join's scratch, used in place) in their allocations; the
+    receive buffers then lie between sentinels (placement.arena)."""
+    import torch
+    from placement import arena, arena_column, check_guards
+    from smj.dist import ceil_log2, owned, plan_shift, used_parts
+    from test_gpu_parity import offset_input
     n = 600_000
     R, S = _inputs(orc, kind, n)
     total, _, _ = orc.sortmergejoin(R, S)
@@ -48,16 +57,16 @@ def test_segmented_join_simulated_exchange(libs, oracles, width, world, kind, pa
     for key, rel in (("R", R), ("S", S)):
         for s in range(world):
             sl = rel[s * n // world:(s + 1) * n // world]
-            d_in = lib.to_device(sl)
+            d_in = offset_input(lib, sl, off)
             hist = torch.zeros(F, dtype=torch.int64, device="cuda")
             if packed:
-                out = torch.empty(len(sl), dtype=torch.int64, device="cuda")
+                out = torch.empty(len(sl) + off, dtype=torch.int64, device="cuda")[off:]
                 bad = torch.zeros(1, dtype=torch.int32, device="cuda")
                 assert lib.dev_partition_range_packed(d_in, out, pbits, 1, n, hist, bad)
                 torch.cuda.synchronize()
                 assert int(bad.item()) == 0
             else:
-                out = lib.empty(len(sl))
+                out = lib.empty(len(sl) + off)[off:]
                 lib.dev_partition_range(d_in, out, pbits, 1, n, hist)
                 torch.cuda.synchronize()
             parts[key, s] = (out, hist)
@@ -76,8 +85,13 @@ def test_segmented_join_simulated_exchange(libs, oracles, width, world, kind, pa
                 cnt = int(hist[p_lo:p_hi].sum())
                 rows.append(out[start:start + cnt])
                 seg[s, :p_hi - p_lo] = hist[p_lo:p_hi]
-            recv[key] = torch.cat(rows).contiguous()
+            rows = torch.cat(rows).contiguous()
+            place = arena_column if packed else arena
+            recv[key] = place(lib, rows.shape[0], off, fill=rows,
+                              **({"dtype": torch.int64} if packed else {})) if off else (None, rows)
             segs[key] = seg
+        arenas = recv
+        recv = {key: view for key, (_, view) in arenas.items()}
         nR, nS = recv["R"].shape[0], recv["S"].shape[0]
         sR, sS = lib.empty(nR), lib.empty(nS)
         cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -92,6 +106,9 @@ def test_segmented_join_simulated_exchange(libs, oracles, width, world, kind, pa
         assert int(cnt.item()) == exp, (g, int(cnt.item()), exp)
         assert np.array_equal(lib.to_host(sR), eR)
         assert np.array_equal(lib.to_host(sS), eS)
+        for key, (buf, view) in arenas.items():
+            if buf is not None:
+                check_guards(buf, view, f"rank {g}: receive buffer {key}")
         got_total += exp
     assert got_total == total
 
@@ -111,14 +128,24 @@ def test_sampled_exchange_simulated(libs, oracles, width, world, kind, layout, s
     stage while S's rows are still in flight).  layout "planes": 48-bit words
     in two planes (smj_dev_partition_range_planes and
     smj_dev_join_segmented_planes), both widths."""
-    import torch
-    from smj.dist import Planes, ceil_log2, owned, plan_shift, used_parts
-    orc, lib = oracles[width], libs[width]
-    packed = layout == "words"
-    if packed and width != 16:
+    if layout == "words" and width != 16:
         pytest.skip("packed words are the 16-byte layout")
     if staged and world == 1:
         pytest.skip("one rank: nothing in flight, the join is one call")
+    sampled_exchange_case(libs[width], oracles[width], world, kind, layout, staged)
+
+
+def sampled_exchange_case(lib, orc, world, kind, layout, staged, off=0):
+    """The sampled exchange and the table-driven join of every rank.  off: the
+    element offset of every partition input, of the tuple or word outputs and
+    of the tuple or word receive buffers in their allocations (the planes
+    keep their documented alignment); the receive buffers then lie between
+    sentinels (placement.arena)."""
+    import torch
+    from placement import arena, arena_column, check_guards
+    from smj.dist import Planes, ceil_log2, owned, plan_shift, used_parts
+    from test_gpu_parity import offset_input
+    packed = layout == "words"
     n = 600_000
     R, S = _inputs(orc, kind, n)
     total, _, _ = orc.sortmergejoin(R, S)
@@ -130,7 +157,7 @@ def test_sampled_exchange_simulated(libs, oracles, width, world, kind, layout, s
     for key, rel in (("R", R), ("S", S)):
         for s in range(world):
             sl = rel[s * n // world:(s + 1) * n // world]
-            d_in = lib.to_device(sl)
+            d_in = offset_input(lib, sl, off)
             cap = lib.sampled_capacity(len(sl), pbits)
             ss = torch.empty(F * K, dtype=torch.int64, device="cuda")
             sc = torch.empty(F * K, dtype=torch.int64, device="cuda")
@@ -141,8 +168,8 @@ def test_sampled_exchange_simulated(libs, oracles, width, world, kind, layout, s
                 assert lib.dev_partition_range_planes(d_in, out.buf, out.stride, pbits, 1, n,
                                                       ss, sc, fl)
             else:
-                out = (torch.full((cap,), -7, dtype=torch.int64, device="cuda") if packed
-                       else lib.empty(cap))
+                out = (torch.full((cap + off,), -7, dtype=torch.int64, device="cuda") if packed
+                       else lib.empty(cap + off))[off:]
                 assert lib.dev_partition_range_sampled(d_in, out, pbits, 1, n, packed, ss, sc,
                                                        fl)
             torch.cuda.synchronize()
@@ -160,7 +187,7 @@ def test_sampled_exchange_simulated(libs, oracles, width, world, kind, layout, s
         lbits = ceil_log2(max(mine, 1))
         key_lo = 1 + (p_lo << s1)
         key_hi = key_lo + (1 << (s1 + lbits)) - 1
-        recv, tabs, used = {}, {}, {}
+        recv, tabs, used, arenas = {}, {}, {}, {}
         for key in ("R", "S"):
             rows, tst, tct, base, nused = [], [], [], 0, 0
             for s in range(world):
@@ -178,6 +205,11 @@ def test_sampled_exchange_simulated(libs, oracles, width, world, kind, layout, s
                 for i in range(2):
                     rb.planes[i][:base].copy_(torch.cat([r[i] for r in rows]))
                 recv[key] = rb
+            elif off:
+                rows = torch.cat(rows).contiguous()
+                arenas[key] = (arena_column if packed else arena)(lib, rows.shape[0], off,
+                                                                  fill=rows)
+                recv[key] = arenas[key][1]
             else:
                 recv[key] = torch.cat(rows).contiguous()
             st_ = torch.zeros(1 << lbits, world * K, dtype=torch.int64, device="cuda")
@@ -218,6 +250,8 @@ def test_sampled_exchange_simulated(libs, oracles, width, world, kind, layout, s
         assert int(cnt.item()) == exp, (g, int(cnt.item()), exp)
         assert np.array_equal(lib.to_host(sR), eR)
         assert np.array_equal(lib.to_host(sS), eS)
+        for key, (buf, view) in arenas.items():
+            check_guards(buf, view, f"rank {g}: receive buffer {key}")
         got_total += exp
     assert got_total == total
 
@@ -342,6 +376,23 @@ def test_rccl_list_all_to_all_views(libs, monkeypatch):
         dist.destroy_process_group()
 
 
+def planes_tuples(out, ss, sc, K, s1, key_min=1):
+    """(key, payload) rows of every region of smj_dev_partition_range_planes'
+    output, regions in table order: element i of the planes is the word
+    lo[i] | hi[i] << 32 = (key - key_min) mod 2^s1 << (48 - s1) | payload, and
+    region r belongs to partition r // K."""
+    lo = out.lo.cpu().numpy().view(np.uint32).astype(np.uint64)
+    hi = out.hi.cpu().numpy().view(np.uint16).astype(np.uint64)
+    w = lo | (hi << np.uint64(32))
+    got = []
+    for i, (a, c) in enumerate(zip(ss.cpu().tolist(), sc.cpu().tolist())):
+        x = w[a:a + c]
+        rel = (np.uint64(i // K) << np.uint64(s1)) | (x >> np.uint64(48 - s1))
+        got.append(np.stack([(rel + np.uint64(key_min)).astype(np.int64),
+                             (x & np.uint64((1 << (48 - s1)) - 1)).astype(np.int64)], 1))
+    return np.concatenate(got)
+
+
 def test_partition_range_planes_flags(libs, width):
     """smj_dev_partition_range_planes' not-packable flags and its limits: a
     payload wider than 48 - s1 bits sets 4 (and 1 past 64 - s1 bits), a key
@@ -374,16 +425,7 @@ def test_partition_range_planes_flags(libs, width):
 
     ok, out, ss, sc, fl = run(keys, pays)
     assert ok and fl == [0, 0] and int(sc.sum()) == n
-    lo = out.lo.cpu().numpy().view(np.uint32).astype(np.uint64)
-    hi = out.hi.cpu().numpy().view(np.uint16).astype(np.uint64)
-    w = lo | (hi << np.uint64(32))
-    got = []
-    for i, (a, c) in enumerate(zip(ss.cpu().tolist(), sc.cpu().tolist())):
-        x = w[a:a + c]
-        rel = (np.uint64(i // K) << np.uint64(s1)) | (x >> np.uint64(48 - s1))
-        got.append(np.stack([(rel + np.uint64(1)).astype(np.int64),
-                             (x & np.uint64((1 << (48 - s1)) - 1)).astype(np.int64)], 1))
-    got = np.concatenate(got)
+    got = planes_tuples(out, ss, sc, K, s1)
     want = np.stack([keys.numpy(), pays.numpy()], 1)
     assert np.array_equal(got[np.lexsort((got[:, 1], got[:, 0]))],
                           want[np.lexsort((want[:, 1], want[:, 0]))])

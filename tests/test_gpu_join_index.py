@@ -144,6 +144,17 @@ def run_pairs(lib, dR, dS, cap, room=5, keys=True):
     return total, [h[:cap] for h in host]
 
 
+def check_pairs(cols, R, S, r_idx, s_idx):
+    """The first len(cols[0]) outputs of dev_join_pairs: the R payloads, the
+    S payloads and, with a third column, the keys (of either side)."""
+    n = len(cols[0])
+    assert np.array_equal(cols[0], R["payload"][r_idx[:n]])
+    assert np.array_equal(cols[1], S["payload"][s_idx[:n]])
+    if len(cols) == 3:
+        assert np.array_equal(cols[2], S["key"][s_idx[:n]])
+        assert np.array_equal(cols[2], R["key"][r_idx[:n]])
+
+
 def test_numpy_construction_against_double_loop():
     """The expected-value construction itself, against the plain definition."""
     R = np.sort(rand_tuples(16, 40, 1, 0, 12), order=["key", "payload"])
@@ -166,10 +177,7 @@ def test_pairs_and_semi(libs, oracles, width, name):
     assert lib.dev_join_pairs(dR, dS) == total  # count only
     got, (r, s, k) = run_pairs(lib, dR, dS, total)
     assert got == total
-    assert np.array_equal(r, R["payload"][r_idx])
-    assert np.array_equal(s, S["payload"][s_idx])
-    assert np.array_equal(k, S["key"][s_idx])
-    assert np.array_equal(k, R["key"][r_idx])
+    check_pairs((r, s, k), R, S, r_idx, s_idx)
     # without the key column
     got, (r2, s2) = run_pairs(lib, dR, dS, total, keys=False)
     assert got == total and np.array_equal(r2, r) and np.array_equal(s2, s)
@@ -211,9 +219,7 @@ def test_capacity(libs, oracles, width):
     cap = total // 3 + 17
     got, (r, s, k) = run_pairs(lib, dR, dS, cap, room=20000)
     assert got == total
-    assert np.array_equal(r, R["payload"][r_idx[:cap]])
-    assert np.array_equal(s, S["payload"][s_idx[:cap]])
-    assert np.array_equal(k, S["key"][s_idx[:cap]])
+    check_pairs((r, s, k), R, S, r_idx, s_idx)
     assert lib.dev_join_pairs(dR, dS) == total
     # semi join into a short buffer
     mask = numpy_semi_mask(R, S)

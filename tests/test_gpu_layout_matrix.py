@@ -12,7 +12,7 @@ edge or a table size can go wrong.
 Expected values are plain numpy (sorted relations and the match count),
 cross-checked once with the oracle where the count is small enough for its
 one-match-per-step merge join.  Every case also checks: the 64 sentinel
-tuples behind both outputs, that the count is overwritten and not added to,
+tuples in front of and behind both outputs, that the count is overwritten and not added to,
 that the inputs are untouched, a second call on the same workspace, the
 layout the call finished in and (kernel trace) whether the exact partition
 and the skew kernels ran.
@@ -684,62 +684,78 @@ def expected(case, width, orc):
 # ---------------------------------------------------------------------------
 # the checks of every case
 # ---------------------------------------------------------------------------
-def _device_in(lib, t):
-    """The relation on the device, a valid pointer also when it is empty."""
-    import torch
-    dt = torch.int32 if lib.width == 8 else torch.int64
-    buf = torch.zeros((len(t) + 1, 2), dtype=dt, device="cuda")
-    if len(t):
-        buf[:len(t)] = lib.to_device(t)
-    return buf[:len(t)]
+def _device_in(lib, t, off=0):
+    """(arena, view): the relation on the device, `off` tuples into its arena
+    (placement.arena); a valid pointer also when it is empty."""
+    from placement import arena
+    return arena(lib, len(t), off, fill=t)
 
 
-def _device_out(lib, n):
-    import torch
-    dt = torch.int32 if lib.width == 8 else torch.int64
-    return torch.full((n + CANARY, 2), SENTINEL, dtype=dt, device="cuda")
+def _device_out(lib, n, off=0):
+    """(arena, view): n output tuples `off` tuples into an arena of
+    sentinels, CANARY of them in front of the view and behind it."""
+    from placement import arena
+    return arena(lib, n, off)
 
 
-def _check_out(lib, buf, n, want, what):
-    got = lib.to_host(buf)
-    assert (got[n:]["key"] == SENTINEL).all() and (got[n:]["payload"] == SENTINEL).all(), \
-        f"{what}: wrote past the {n} output tuples"
-    assert np.array_equal(got[:n], want), f"{what}: sorted relation differs"
+def _check_out(lib, buf, view, want, what):
+    from placement import check_guards
+    check_guards(buf, view, f"{what}: output")
+    assert np.array_equal(lib.to_host(view), want), f"{what}: sorted relation differs"
 
 
-def run_case(lib, orc, case):
+def run_case(lib, orc, case, placement=None):
     """The case (a join or a sort), twice on one fresh workspace, with all the
-    checks of the module docstring."""
+    checks of the module docstring.  placement: the tuple offsets of the
+    buffers in their arenas, (R_in, S_in, R_out, S_out) for a join, (in, out)
+    for a sort, or ("inplace", off) for a sort whose output is its input;
+    None: all 0."""
     import torch
+    from placement import check_guards
     width = lib.width
     if case.expect[width] is None:
         return "skip"
     rels, srt, cnt = expected(case, width, orc)
+    k = len(rels)
+    inplace = placement is not None and placement[0] == "inplace"
+    if placement is None:
+        placement = (0,) * (2 * k)
+    elif inplace:
+        assert case.kind == "sort"
+        placement = (placement[1], placement[1])
+    assert len(placement) == 2 * k
     lib.reset_workspace()
     lib.set_layouts(case.flags)
     try:
-        ins = [_device_in(lib, t) for t in rels]
+        ins = [_device_in(lib, t, off) for t, off in zip(rels, placement[:k])]
         for call in range(2):
             what = f"{case.name} w{width} call {call}"
-            outs = [_device_out(lib, len(t)) for t in rels]
+            if inplace:
+                if call:
+                    ins = [_device_in(lib, t, off) for t, off in zip(rels, placement[:k])]
+                outs = ins
+            else:
+                outs = [_device_out(lib, len(t), off) for t, off in zip(rels, placement[k:])]
             count = torch.full((1,), 0x7EADBEEF, dtype=torch.int64, device="cuda")
             lib.trace(True)
             if case.kind == "join":
                 lo, hi = case.hint if case.hint is not None else (1, 0)
-                lib.dev_join(ins[0], ins[1], outs[0][:case.nR], outs[1][:case.nS], count,
+                lib.dev_join(ins[0][1], ins[1][1], outs[0][1], outs[1][1], count,
                              case.fanout, lo, hi)
             else:
-                lib.dev_sort(ins[0], outs[0][:case.nR])
+                lib.dev_sort(ins[0][1], outs[0][1])
             torch.cuda.synchronize()
             trace = lib.trace_read()
             lib.trace(False)
             ran = {k for k, (_, launches) in trace.items() if launches > 0}
             if case.kind == "join":
                 assert int(count.item()) == cnt, f"{what}: count {int(count.item())} != {cnt}"
-            for buf, t, name in zip(outs, srt, "RS"):
-                _check_out(lib, buf, len(t), t, f"{what} {name}")
-            for d, t, name in zip(ins, rels, "RS"):
-                assert np.array_equal(lib.to_host(d), t), f"{what}: input {name} changed"
+            for (buf, view), t, name in zip(outs, srt, "RS"):
+                _check_out(lib, buf, view, t, f"{what} {name}")
+            if not inplace:
+                for (buf, view), t, name in zip(ins, rels, "RS"):
+                    assert np.array_equal(lib.to_host(view), t), f"{what}: input {name} changed"
+                    check_guards(buf, view, f"{what}: input {name}")
             seen = (lib.last_layout(), "k_hist" in ran,
                     bool(ran & {"k_skew_small", "k_skew_hist"}))
             assert seen[0] == case.layout(width, call), f"{what}: layout {seen[0]}"
@@ -752,8 +768,8 @@ def run_case(lib, orc, case):
     return "ran"
 
 
-def run_cases(libs, oracles, width, cases):
-    done = [run_case(libs[width], oracles[width], c) for c in cases]
+def run_cases(libs, oracles, width, cases, placement=None):
+    done = [run_case(libs[width], oracles[width], c, placement) for c in cases]
     if "ran" not in done:
         pytest.skip(cases[0].why)
 

@@ -629,21 +629,43 @@ def test_partition_range_sampled_small_bits(libs, oracles, width, nbits, n, pack
     overestimate is largest against the per-region slack: every region must
     stay inside smj_sampled_capacity() (a canary after it stays intact) and
     the partitions must hold exactly the input, each key in its range."""
-    import torch
-    orc, lib = oracles[width], libs[width]
     if packed and width != 16:
         pytest.skip("packed words are the 16-byte layout")
+    partition_range_sampled_case(libs[width], oracles[width], nbits, n, packed)
+
+
+def offset_input(lib, t, off):
+    """The relation on the device, `off` tuples into its allocation."""
+    full = lib.empty(len(t) + off)
+    d_in = full[off:]
+    d_in.copy_(lib.to_device(t))
+    if lib.width == 8 and off % 2:
+        assert d_in.data_ptr() % 16 == 8
+    return d_in
+
+
+def canary_output(lib, n, off, words, canary=4096):
+    """(allocation, view): n tuples (or int64 words) `off` elements into an
+    allocation of -7s that goes on for `canary` elements behind them."""
+    import torch
+    if words:
+        full = torch.full((off + n + canary,), -7, dtype=torch.int64, device="cuda")
+    else:
+        full = lib.empty(off + n + canary)
+        full.fill_(-7)
+    return full, full[off:]
+
+
+def partition_range_sampled_case(lib, orc, nbits, n, packed, in_off=0, out_off=0):
+    """The checks of test_partition_range_sampled_small_bits, with the input
+    and the output in_off / out_off elements into their allocations."""
+    import torch
     orc.seed(99 + n)
     t = orc.create_relation_pk(n)
-    d_in = lib.to_device(t)
+    d_in = offset_input(lib, t, in_off)
     F, K = 1 << nbits, lib.sampled_shards()
     cap = lib.sampled_capacity(n, nbits)
-    canary = 4096
-    if packed:
-        buf = torch.full((cap + canary,), -7, dtype=torch.int64, device="cuda")
-    else:
-        buf = lib.empty(cap + canary)
-        buf.fill_(-7)
+    full, buf = canary_output(lib, cap, out_off, packed)
     ss = torch.empty(F * K, dtype=torch.int64, device="cuda")
     sc = torch.empty(F * K, dtype=torch.int64, device="cuda")
     fl = torch.ones(2, dtype=torch.int32, device="cuda")
@@ -652,7 +674,8 @@ def test_partition_range_sampled_small_bits(libs, oracles, width, nbits, n, pack
         assert packed and int(n - 1).bit_length() - nbits < 1
         return
     torch.cuda.synchronize()
-    assert bool((buf[cap:] == -7).all())
+    assert bool((buf[cap:] == -7).all()) and bool((full[:out_off] == -7).all())
+    assert np.array_equal(lib.to_host(d_in), t)
     if fl[0]:
         # a region overflowed (few workgroups fill few of a partition's shards:
         # the join then repeats the exact partition); nothing passed the buffer
@@ -686,21 +709,21 @@ def test_partition_range_shards(libs, oracles, width, nbits, n, packed):
     partitions together are exactly the input (16-byte tuples: the (key,
     payload) multiset; packed words: per partition the same sorted words as
     smj_dev_partition_range_packed writes)."""
-    import torch
-    orc, lib = oracles[width], libs[width]
     if packed and width != 16:
         pytest.skip("packed words are the 16-byte layout")
+    partition_range_shards_case(libs[width], oracles[width], nbits, n, packed)
+
+
+def partition_range_shards_case(lib, orc, nbits, n, packed, in_off=0, out_off=0):
+    """The checks of test_partition_range_shards, with the input and the
+    output in_off / out_off elements into their allocations."""
+    import torch
     orc.seed(7 + n + nbits)
     t = orc.create_relation_fk(n, 5 * n)
     t["payload"] = np.arange(n)
-    d_in = lib.to_device(t)
+    d_in = offset_input(lib, t, in_off)
     F, K = 1 << nbits, lib.sampled_shards()
-    canary = 4096
-    if packed:
-        buf = torch.full((n + canary,), -7, dtype=torch.int64, device="cuda")
-    else:
-        buf = lib.empty(n + canary)
-        buf.fill_(-7)
+    full, buf = canary_output(lib, n, out_off, packed)
     ss = torch.empty(F * K, dtype=torch.int64, device="cuda")
     sc = torch.empty(F * K, dtype=torch.int64, device="cuda")
     fl = torch.ones(2, dtype=torch.int32, device="cuda")
@@ -711,13 +734,15 @@ def test_partition_range_shards(libs, oracles, width, nbits, n, packed):
     torch.cuda.synchronize()
     assert fl.tolist() == [0, 0]
     assert bool((buf[n:] == -7).all())  # nothing past n
+    assert bool((full[:out_off] == -7).all())  # nor in front of the output
+    assert np.array_equal(lib.to_host(d_in), t)
     ssh, sch = ss.cpu().numpy(), sc.cpu().numpy()
     assert int(sch.sum()) == n
     # back to back: region i starts where region i - 1 ends
     assert ssh[0] == 0 and np.array_equal(ssh[1:], (ssh + sch)[:-1])
     s1 = max(int(kmax - 1).bit_length() - nbits, 0)
     if packed:
-        words = torch.empty(n, dtype=torch.int64, device="cuda")
+        words = canary_output(lib, n, out_off, True, canary=0)[1]
         hist = torch.zeros(F, dtype=torch.int64, device="cuda")
         bad = torch.zeros(1, dtype=torch.int32, device="cuda")
         assert lib.dev_partition_range_packed(d_in, words, nbits, 1, kmax, hist, bad)
