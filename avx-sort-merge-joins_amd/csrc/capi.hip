@@ -1853,6 +1853,29 @@ void smj_dev_band_join_count(smj_workspace* ws, const tuple_t* sortedR, uint64_t
                     count_dev, (hipStream_t)stream);
 }
 
+static_assert(SMJ_ASOF_BACKWARD == kAsofBackward && SMJ_ASOF_FORWARD == kAsofForward &&
+              SMJ_ASOF_NEAREST == kAsofNearest, "smj.h / asofjoin.hip directions");
+
+void smj_dev_asof_join(smj_workspace* ws, const tuple_t* sortedR, uint64_t nR,
+                       const tuple_t* sortedS, uint64_t nS, uint32_t mode, uint64_t tolerance,
+                       uint32_t group_shift, int64_t* r_index_out, value_t* r_payload_out,
+                       intkey_t* r_key_out, unsigned long long* matched_dev,
+                       smj_stream_t stream) {
+    const uint32_t dir = mode & ~SMJ_ASOF_STRICT;
+    if (dir > SMJ_ASOF_NEAREST) {
+        fprintf(stderr, "[ERROR] smj_dev_asof_join: mode %u is no SMJ_ASOF_* direction "
+                "(with or without SMJ_ASOF_STRICT)\n", mode);
+        abort();
+    }
+    if (group_shift > 63) {
+        fprintf(stderr, "[ERROR] smj_dev_asof_join: group_shift %u is above 63\n", group_shift);
+        abort();
+    }
+    asof_join((Workspace*)ws, (const Tup*)sortedR, nR, (const Tup*)sortedS, nS, dir,
+              (mode & SMJ_ASOF_STRICT) != 0, tolerance, group_shift, r_index_out, r_payload_out,
+              r_key_out, matched_dev, (hipStream_t)stream);
+}
+
 void smj_dev_join(smj_workspace* ws, const tuple_t* R, uint64_t nR,
                   const tuple_t* S, uint64_t nS, tuple_t* sortedR,
                   tuple_t* sortedS, uint32_t fanout_bits, int64_t key_min,

@@ -465,6 +465,18 @@ uint64_t band_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint6
 void band_join_count(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
                      int64_t lo, int64_t hi, unsigned long long* count_dev, hipStream_t st);
 
+// ---- asofjoin.hip : as-of join of sorted R and S (smj.h smj_dev_asof_join)
+// Per S tuple one partner in R: the last at or before its key, the first at
+// or after it, or the closer of the two (dir; the values of SMJ_ASOF_*),
+// within `tolerance` and the key group of `group_shift` (0..63, 0: none).  Row
+// i of every non-null column belongs to S[i]; the matched rows are added to
+// *matched_dev unless it is null.  Stream-ordered, no synchronisation.
+constexpr uint32_t kAsofBackward = 0, kAsofForward = 1, kAsofNearest = 2;
+void asof_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
+               uint32_t dir, bool strict, uint64_t tolerance, uint32_t group_shift,
+               int64_t* r_index_out, void* r_payload_out, void* r_key_out,
+               unsigned long long* matched_dev, hipStream_t st);
+
 // ---- datagen.hip
 void gen_pk(Tup* out, uint64_t n, uint64_t first, uint64_t total,
             uint64_t seed, hipStream_t st);

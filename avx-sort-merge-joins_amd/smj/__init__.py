@@ -71,8 +71,11 @@ DEVICE_SYMBOLS = [
     "smj_mgpu_last_stats", "smj_mgpu_last_sorted", "smj_mgpu_group_workspace",
     "smj_dev_partition_range_shards", "smj_tilepass_occupancy",
     "smj_dev_join_pairs", "smj_dev_semi_join",
-    "smj_dev_band_join", "smj_dev_band_join_count",
+    "smj_dev_band_join", "smj_dev_band_join_count", "smj_dev_asof_join",
 ]
+# smj_dev_asof_join's mode (SMJ_ASOF_* in smj.h)
+ASOF_DIRECTIONS = {"backward": 0, "forward": 1, "nearest": 2}
+ASOF_STRICT = 4
 
 
 def lib_path(width: int) -> str:
@@ -285,6 +288,8 @@ class Library:
             "smj_dev_band_join": (_U64, [_P, _P, _U64, _P, _U64, _I64, _I64, _P, _P, _P, _P,
                                          _U64, _P]),
             "smj_dev_band_join_count": (None, [_P, _P, _U64, _P, _U64, _I64, _I64, _P, _P]),
+            "smj_dev_asof_join": (None, [_P, _P, _U64, _P, _U64, _U32, _U64, _U32, _P, _P, _P,
+                                         _P, _P]),
             "smj_selfcheck_lds_order": (_U64, [_P, _P]),
             "smj_context_workspace": (_P, []),
             "smj_dev_gen_nonunique": (None, [_P, _P, _U64, _U64, _U64, _I64, _U32, _U64, _P]),
@@ -835,6 +840,69 @@ class Library:
             got = self.dev_band_join(sR, sS, lo, hi, *cols)
             assert got == total, (got, total)
         return tuple(cols)
+
+    @staticmethod
+    def _asof(direction, strict, tolerance, group_shift):
+        """(mode, tolerance, group_shift) of smj_dev_asof_join, checked here:
+        the library aborts on a value it does not take."""
+        assert direction in ASOF_DIRECTIONS, f"direction is one of {sorted(ASOF_DIRECTIONS)}"
+        mode = ASOF_DIRECTIONS[direction] | (ASOF_STRICT if strict else 0)
+        tol = (1 << 64) - 1 if tolerance is None else int(tolerance)
+        assert 0 <= tol < (1 << 64), "tolerance is uint64 (None: no limit)"
+        group_shift = int(group_shift)
+        assert 0 <= group_shift <= 63, "group_shift is 0 (no groups) to 63"
+        return mode, tol, group_shift
+
+    def _asof_column(self, t, n, what, dtype=None):
+        dt = dtype or (torch.int32 if self.width == 8 else torch.int64)
+        assert t.dim() == 1 and t.dtype == dt and t.is_contiguous() and t.is_cuda, what
+        assert t.shape[0] >= n, f"{what} holds fewer than the {n} rows of sortedS"
+        return t.data_ptr()
+
+    def dev_asof_join(self, sortedR, sortedS, direction="backward", strict=False,
+                      tolerance=None, group_shift=0, r_index=None, r_payload=None,
+                      r_key=None, matched=None):
+        """As-of join (smj_dev_asof_join): for row i of sortedS one partner in
+        sortedR -- the last tuple at or before its key ("backward"), the first
+        at or after it ("forward") or the closer of the two ("nearest", the
+        earlier one on equal distances); strict: equal keys are no partners.
+        tolerance: the largest |s.key - r.key| that counts (None: no limit);
+        group_shift: 1..63 keeps partners inside (key >> group_shift), 0: no
+        groups.  Each column given gets len(sortedS) rows: r_index (int64) the
+        partner's position in sortedR or -1, r_payload and r_key (the payload
+        dtype) its payload and key or 0.  The matched rows are added to
+        matched[0] (int64 device tensor).  Stream-ordered; returns nothing."""
+        mode, tol, gsh = self._asof(direction, strict, tolerance, group_shift)
+        n = sortedS.shape[0]
+        ip = self._asof_column(r_index, n, "r_index", torch.int64) if r_index is not None else None
+        pp = self._asof_column(r_payload, n, "r_payload") if r_payload is not None else None
+        kp = self._asof_column(r_key, n, "r_key") if r_key is not None else None
+        mp = self._asof_column(matched, 1, "matched", torch.int64) if matched is not None else None
+        self.lib.smj_dev_asof_join(
+            self.ws, sortedR.data_ptr(), sortedR.shape[0], sortedS.data_ptr(), n, mode, tol,
+            gsh, ip, pp, kp, mp, self.stream_ptr())
+
+    def asof_join(self, R, S, direction="backward", strict=False, tolerance=None,
+                  group_shift=0, with_keys=False):
+        """The as-of join of two unsorted device relations in one call: sorts
+        both (dev_sort) into temporaries and joins them (dev_asof_join).
+        Returns 1-D tensors of len(S) rows in sorted-S order on the current
+        stream: (s_payloads, r_payloads, matched_mask[, s_keys, r_keys]);
+        matched_mask is bool, and r_payloads / r_keys are 0 where it is
+        False."""
+        dt = torch.int32 if self.width == 8 else torch.int64
+        nR, nS = R.shape[0], S.shape[0]
+        sR, sS = self.empty(nR), self.empty(nS)
+        if nR:
+            self.dev_sort(R, sR)
+        if nS:
+            self.dev_sort(S, sS)
+        idx = torch.empty(nS, dtype=torch.int64, device=S.device)
+        cols = [torch.empty(nS, dtype=dt, device=S.device) for _ in range(2 if with_keys else 1)]
+        if nS:
+            self.dev_asof_join(sR, sS, direction, strict, tolerance, group_shift, idx, *cols)
+        out = (sS[:, 0].contiguous(), cols[0], idx >= 0)
+        return out + (sS[:, 1].contiguous(), cols[1]) if with_keys else out
 
     def dev_join(self, R, S, sortedR, sortedS, count, fanout_bits=10,
                  key_min=1, key_max=0):

@@ -676,6 +676,58 @@ void smj_dev_band_join_count(smj_workspace * ws, const tuple_t * sortedR, uint64
                              const tuple_t * sortedS, uint64_t nS, int64_t lo, int64_t hi,
                              unsigned long long * count_dev, smj_stream_t stream);
 
+/* As-of join of two sorted relations: for every S tuple ONE partner in R, the
+ * nearest R tuple at or before its key, at or after it, or on either side
+ * ("the quote in force at each trade", merge_asof, ASOF JOIN; the library's
+ * own, and like the band join one that only a sort-based library offers).
+ * mode: one of the directions below, optionally or-ed with SMJ_ASOF_STRICT;
+ *   any other value aborts with a message. */
+#define SMJ_ASOF_BACKWARD 0u  /* B: the last position p with sortedR[p].key <= s.key  */
+#define SMJ_ASOF_FORWARD  1u  /* F: the first position p with sortedR[p].key >= s.key */
+#define SMJ_ASOF_NEAREST  2u  /* B or F, the smaller |s.key - r.key|; equal: B        */
+#define SMJ_ASOF_STRICT   4u  /* or-ed in: equal keys are no partners (< and >)       */
+/* Candidates: taken by position in the sorted arrays, so the result is
+ *   deterministic given the sorted inputs (8-byte tie order included): among
+ *   R tuples with equal keys backward takes the last and forward the first.
+ *   With SMJ_ASOF_STRICT B is the last position with a key < s.key and F the
+ *   first with a key > s.key.
+ * tolerance: a candidate counts only if |s.key - r.key| <= tolerance, the
+ *   distance taken as an unsigned 64-bit value without wrap-around (the
+ *   difference of two int64 keys fits; the 8-byte library widens its int32
+ *   keys first).  UINT64_MAX: no limit.
+ * group_shift: 0 for no groups; for 1..63 a candidate counts only if
+ *   (r.key >> group_shift) == (s.key >> group_shift), an arithmetic shift of
+ *   the key widened to int64 -- the `by` of an as-of join for keys built as
+ *   group << t | time.  The shift is monotone, so a group is one contiguous
+ *   range of sortedR and the filter on the two candidates is exact: if B lies
+ *   in a lower group, no R tuple of the S tuple's group is at or before it.
+ *   Values above 63 abort with a message.
+ * SMJ_ASOF_NEAREST: B and F are each filtered on their own by tolerance and
+ *   group; of the survivors the one at the smaller distance wins, B on equal
+ *   distances.
+ * Output: row i belongs to sortedS[i], and every non-NULL column gets all nS
+ *   rows: a matched row the partner's position in sortedR (r_index_out), its
+ *   payload and its key; an unmatched row -1 in r_index_out and 0 in the other
+ *   two.  Nothing is written beyond row nS - 1.  The number of matched rows
+ *   is ADDED to *matched_dev (device), like smj_dev_band_join_count's count,
+ *   unless it is NULL.  All three columns NULL with matched_dev non-NULL is
+ *   the count form; everything NULL launches nothing.
+ * Empty calls: nS == 0 launches nothing; nR == 0 writes every row as
+ *   unmatched and adds 0.
+ * Order: stream-ordered, no host synchronisation (the workspace's tables
+ *   grow on a first call).  The inputs are left untouched; the outputs must
+ *   not overlap them.  Alignment as for the rest of the device API:
+ *   tuple-granular slices of a hipMalloc buffer, columns aligned to their
+ *   element. */
+void smj_dev_asof_join(smj_workspace * ws, const tuple_t * sortedR, uint64_t nR,
+                       const tuple_t * sortedS, uint64_t nS, uint32_t mode,
+                       uint64_t tolerance, uint32_t group_shift,
+                       int64_t * r_index_out /* may be NULL */,
+                       value_t * r_payload_out /* may be NULL */,
+                       intkey_t * r_key_out /* may be NULL */,
+                       unsigned long long * matched_dev /* may be NULL */,
+                       smj_stream_t stream);
+
 /* The m-way join on one device.  R and S are left untouched; sortedR/sortedS
  * (n tuples each) receive the fully sorted relations; the match count is
  * written to *count_dev.  key_min <= key_max is an optional hint of the key
