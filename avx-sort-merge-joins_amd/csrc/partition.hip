@@ -1432,11 +1432,17 @@ k_scatter_res(const Tup* __restrict__ in, uint64_t n, uint64_t chunk, Digit dig_
     // one partition per thread (the host launches nbins <= THREADS): the
     // per-partition state lives in registers, no dynamic indexing
     const uint32_t d0 = threadIdx.x;
-    const bool own = d0 < nbins;
-    const uint64_t my_cap = own ? cap_end[(size_t)d0 * kShards] : 0;
+    const bool own_thread = d0 < nbins;
+    const uint64_t my_cap = own_thread ? cap_end[(size_t)d0 * kShards] : 0;
     uint32_t my_kc = 0;
 
     static_assert(!VEC || (sizeof(Tup) == 8 && ITEMS % 2 == 0), "VEC: 8-byte tuples, ITEMS even");
+    // load instructions of one tile a thread, and the s_waitcnt operand
+    // "at most NLOADS vector-memory operations pending, nothing else waited
+    // for" (gfx9: vmcnt in bits 3:0 and 15:14, expcnt 7, lgkmcnt 15)
+    constexpr int NLOADS = VEC ? ITEMS / 2 : ITEMS;
+    static_assert(NLOADS < 64, "vmcnt is a 6-bit counter");
+    constexpr int kWaitPrefetch = 0x0f70 | (NLOADS & 15) | ((NLOADS >> 4) << 14);
     // tile position of item j (VEC: pairs of adjacent tuples per thread)
     auto item_pos = [](int j) -> uint32_t {
         return VEC ? 2u * ((uint32_t)(j / 2) * THREADS + threadIdx.x) + (uint32_t)(j & 1)
@@ -1473,14 +1479,35 @@ k_scatter_res(const Tup* __restrict__ in, uint64_t n, uint64_t chunk, Digit dig_
     Tup v[ITEMS], nv[ITEMS];
     if (beg < end) load_tile(v, beg);
     __syncthreads();
+    // Two wave classes run the tile loop as two copies of its code (the wait
+    // counter is per wave, and in one copy the compiler's count cannot tell
+    // the classes apart: it drains the early loads before the late ones reuse
+    // their registers).  Waves with an owner thread (threadIdx.x < nbins)
+    // reserve output space and issue the reservation before the prefetch, to
+    // wait for it alone with vmcnt(NLOADS).  The others (EARLY) issue nothing
+    // but the tile's loads and stores: their prefetch starts at the top of
+    // the iteration, under the rank and the scan, and their only wait is the
+    // vmcnt(0) there.  Both copies execute the same barriers.  (The loop
+    // keeps its indentation inside the lambda.)
+    auto tiles = [&, stage, carry, pos, tstart, tfill, kc, segpre, segown, scr, cursor, out,
+                  ostride, nbins, beg, end, d0, my_cap, own_thread](auto early_c) {
+    constexpr bool EARLY = decltype(early_c)::value;
+    const bool own = EARLY ? false : own_thread;
     for (uint64_t base = beg; base < end; base += TILE) {
         const uint32_t tcount =
             (uint32_t)((end - base) < (uint64_t)TILE ? (end - base) : TILE);
         const uint64_t nb = base + TILE;
         // this tile's loads (the previous prefetch) have landed: an explicit
-        // vmcnt(0) on every path, so the compiler's own bookkeeping does not
-        // re-wait (for the next prefetch) at each conditional use below
+        // vmcnt(0) on every path.  It is one of the two places the kernel
+        // waits on the vector-memory counter by hand; the other is the owner
+        // waves' vmcnt(NLOADS) behind the staging below.  With both in place
+        // the compiler adds no wait of its own between the prefetch and the
+        // last segment store (read in the device assembly of the instances
+        // launched; tools/scan_waits.py --store-waits lists offenders.  The
+        // 16-item tile of 8-byte tuples is one: it spills my_cap, and the
+        // reload under `if (own)` drains the owner waves' counter)
         __builtin_amdgcn_s_waitcnt(0x0f70);
+        if constexpr (EARLY) load_tile(nv, nb);
         // ---- rank: tile counts per partition
         uint32_t dg[ITEMS];
 #pragma unroll
@@ -1509,13 +1536,20 @@ k_scatter_res(const Tup* __restrict__ in, uint64_t n, uint64_t chunk, Digit dig_
             // it (after the staging below) does not wait for that prefetch
             if (Eown) Pown = atomicAdd(&cursor[(size_t)d0 * kShards], (unsigned long long)Eown);
         }
-        // unconditional (clamped) loads: a fixed count in flight lets the
-        // reservation results be waited for with vmcnt(ITEMS)
-        load_tile(nv, nb);
+        // unconditional (clamped) loads: a fixed count in flight (NLOADS a
+        // thread) lets the reservation be waited for with vmcnt(NLOADS)
+        if constexpr (!EARLY) load_tile(nv, nb);
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < ITEMS; j++)
             if (dg[j] != 0xffffffffu) stage[atomicAdd(&tfill[dg[j]], 1u)] = pk(v[j], bad);
+        // the reservation has returned, on every path: only the owner threads
+        // read it, but a wait under `if (own)` alone leaves it pending on the
+        // other paths in the compiler's count, which then drains the counter
+        // (prefetch included) in front of the segment stores and again in
+        // front of the carry.  After this wait the prefetch is waited for only
+        // where `v = nv` copies it, behind the stores and the carry.
+        if constexpr (!EARLY) __builtin_amdgcn_s_waitcnt(kWaitPrefetch);
         if (own) {
             // an overflowing region writes nothing (the caller repeats the
             // exact partition)
@@ -1576,7 +1610,10 @@ k_scatter_res(const Tup* __restrict__ in, uint64_t n, uint64_t chunk, Digit dig_
                 const uint32_t e = (sg - segpre[d]) * SEG + q % SEG;
                 const uint32_t k = kc[d];
                 const uint64_t p = pos[d];
-                const OutT x = e < k ? carry[d * SEG + e] : stage[tstart[d] + e - k];
+                // one base, the index selected (carry = stage + TILE): a
+                // select between two pointers to a struct loses their
+                // address space
+                const OutT x = stage[e < k ? TILE + d * SEG + e : tstart[d] + e - k];
                 if (p != ~0ull) Pack::store(out, ostride, p + e, x);
             }
         }
@@ -1596,6 +1633,19 @@ k_scatter_res(const Tup* __restrict__ in, uint64_t n, uint64_t chunk, Digit dig_
         for (int j = 0; j < ITEMS; j++) v[j] = nv[j];
         __syncthreads();
     }
+    };  // tiles
+    // The early copy keeps v, nv and dg live through the rank and the scan.
+    // That fits the 128 VGPRs of a 1024-thread workgroup for 16-byte tuples
+    // (at most 128, no scratch) and for the 8-item tile of 8-byte tuples; the
+    // 12- and 16-item tiles of 8-byte tuples would spill (12 to 76 bytes of
+    // scratch a lane) and keep the one copy.
+    constexpr bool kSplit = sizeof(Tup) == 16 || ITEMS <= 8;
+    // wave-uniform: the first lane's thread index is the wave's base
+    if (kSplit && (uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= nbins)
+        tiles(std::true_type{});
+    else
+        tiles(std::false_type{});
+    const bool own = own_thread;
     // ---- flush the carries: reserve exactly what is left
     if (own) {
         const uint32_t d = d0;
