@@ -1876,6 +1876,32 @@ void smj_dev_asof_join(smj_workspace* ws, const tuple_t* sortedR, uint64_t nR,
               r_key_out, matched_dev, (hipStream_t)stream);
 }
 
+static void check_group_shift(const char* fn, uint32_t group_shift) {
+    if (group_shift > 63) {
+        fprintf(stderr, "[ERROR] %s: group_shift %u is above 63\n", fn, group_shift);
+        abort();
+    }
+}
+
+uint64_t smj_dev_group_aggregate(smj_workspace* ws, const tuple_t* sorted, uint64_t n,
+                                 uint32_t group_shift, intkey_t* key_out, int64_t* start_out,
+                                 int64_t* count_out, int64_t* sum_out, value_t* min_out,
+                                 value_t* max_out, uint64_t out_cap, smj_stream_t stream) {
+    check_group_shift("smj_dev_group_aggregate", group_shift);
+    return group_aggregate((Workspace*)ws, (const Tup*)sorted, n, group_shift, key_out, start_out,
+                           count_out, sum_out, min_out, max_out, out_cap, (hipStream_t)stream);
+}
+
+void smj_dev_group_count(smj_workspace* ws, const tuple_t* sorted, uint64_t n,
+                         uint32_t group_shift, unsigned long long* groups_dev,
+                         smj_stream_t stream) {
+    check_group_shift("smj_dev_group_count", group_shift);
+    group_count((Workspace*)ws, (const Tup*)sorted, n, group_shift, groups_dev,
+                (hipStream_t)stream);
+}
+
+uint32_t smj_group_tile(void) { return group_tile(); }
+
 void smj_dev_join(smj_workspace* ws, const tuple_t* R, uint64_t nR,
                   const tuple_t* S, uint64_t nS, tuple_t* sortedR,
                   tuple_t* sortedS, uint32_t fanout_bits, int64_t key_min,

@@ -1,0 +1,568 @@
+// groupagg.hip -- grouped aggregation of one sorted relation (smj.h
+// smj_dev_group_aggregate): one output row per maximal run of equal
+// key >> group_shift, with the run's first key, start, length and the sum,
+// minimum and maximum of its payloads.  The library's own; the reference has
+// joins only.
+//
+// A run does not respect tile boundaries (a hot key spans thousands of
+// tiles), and no workgroup may wait for another, so the passes are the
+// project's count -> scan -> write with one more step over the tiles only:
+//   k_group_count one workgroup per tile of GA_TILE elements, every wave a
+//                 chunk of GA_CHUNK consecutive ones (lane l of round j holds
+//                 element 64 j + l of it).  Element i is a head when i == 0 or
+//                 its group differs from that of element i - 1 (the first
+//                 element of a chunk reads one key in front of it).  Leaves
+//                 the tile's number of heads and its open tail: the
+//                 aggregate from its last head to its end (of the whole tile
+//                 when it has no head) and that head's position, or none;
+//   k_mat_scan    materialize.hip's, over the head counts: the heads in front
+//                 of every tile, which number its rows, and the total;
+//   k_group_carry a segmented scan of the tails over the tiles (three small
+//                 kernels over ntiles items, GC_BLOCK tiles a workgroup): for
+//                 every tile the aggregate and the start of the part of the
+//                 group open at its first element that lies in earlier
+//                 tiles.  A tile without a head passes its predecessor's
+//                 carry on, combined with its own;
+//   k_group_write one workgroup per tile: reads the tile again, forms the
+//                 inclusive aggregates of the runs with a segmented scan over
+//                 the lanes of each round, carried from round to round in
+//                 registers and from wave to wave through LDS, and writes a
+//                 row at every element that ends its group (the next element
+//                 is a head or lies behind the relation; the last element of
+//                 a chunk reads one key behind it).  The row of a group is
+//                 the rank of its head, so consecutive ends -- consecutive
+//                 lanes -- write consecutive rows of every column.  An end
+//                 whose head lies in front of its chunk combines what came in
+//                 from the earlier waves and the tile's carry.
+// Where a head lies and how many precede a lane come from the rounds' head
+// ballots; only sum, minimum and maximum go through the scan.  With a group
+// shift the first key of a run is not the key of its end: the end reads it
+// from the relation at the run's start (one key per row, not a pass).
+// smj_dev_group_count is the count pass over the keys alone and a reduction.
+#include "smj_common.hpp"
+#include "smj_internal.hpp"
+#include "mat_common.hpp"
+
+namespace smj {
+
+constexpr int GA_THREADS = MT_THREADS;
+constexpr int GA_WAVES = GA_THREADS / 64;
+constexpr int GA_IPT = 4;                             // rounds of 64 elements a wave
+constexpr uint32_t GA_CHUNK = 64 * GA_IPT;            // consecutive elements of a wave
+constexpr uint32_t GA_TILE = GA_WAVES * GA_CHUNK;     // elements of a workgroup
+constexpr uint32_t GC_BLOCK = 1024;                   // tiles of a carry workgroup
+constexpr uint64_t kNoHead = ~0ull;
+
+uint32_t group_tile() { return GA_TILE; }
+
+// the output columns (each may be null)
+struct GroupCols {
+    MatVal* key;
+    int64_t* start;
+    int64_t* count;
+    int64_t* sum;
+    MatVal* mn;
+    MatVal* mx;
+};
+
+// sum, minimum and maximum of some payloads, in registers
+struct GAgg {
+    int64_t sum;
+    MatVal mn, mx;
+};
+
+#ifdef KEY_8B
+constexpr MatVal kValMax = INT64_MAX, kValMin = INT64_MIN;
+#else
+constexpr MatVal kValMax = INT32_MAX, kValMin = INT32_MIN;
+#endif
+
+__device__ __forceinline__ GAgg ga_none() { return GAgg{0, kValMax, kValMin}; }
+
+template <class T>
+__device__ __forceinline__ T vmin(T a, T b) { return b < a ? b : a; }
+template <class T>
+__device__ __forceinline__ T vmax(T a, T b) { return b > a ? b : a; }
+
+__device__ __forceinline__ GAgg ga_comb(const GAgg& a, const GAgg& b) {
+    return GAgg{(int64_t)((uint64_t)a.sum + (uint64_t)b.sum), vmin(a.mn, b.mn), vmax(a.mx, b.mx)};
+}
+
+// a tile's (a range of tiles') open tail in the tables: the aggregate behind
+// its last head, at `start`, or of all of it when it has none (kNoHead)
+struct GCarry {
+    int64_t sum, mn, mx;
+    uint64_t start;
+};
+
+// (the ends of the payload type, so that the tables' values always fit it)
+__device__ __forceinline__ GCarry gc_none() {
+    return GCarry{0, (int64_t)kValMax, (int64_t)kValMin, kNoHead};
+}
+
+// a then b: a head in b closes what a left open.  Field by field: a select
+// between two structs can go through scratch memory
+__device__ __forceinline__ GCarry gc_comb(const GCarry& a, const GCarry& b) {
+    const bool cut = b.start != kNoHead;
+    GCarry r;
+    r.sum = cut ? b.sum : (int64_t)((uint64_t)a.sum + (uint64_t)b.sum);
+    r.mn = cut ? b.mn : vmin(a.mn, b.mn);
+    r.mx = cut ? b.mx : vmax(a.mx, b.mx);
+    r.start = cut ? b.start : a.start;
+    return r;
+}
+
+// Lane moves of the scans as DPP modifiers of VALU moves (row_shr:n inside a
+// row of 16 lanes, row_bcast:15 / row_bcast:31 across rows, wave_shr:1), not
+// ds_bpermute: the write pass is bound by them.  A lane without a source keeps
+// its own value.
+constexpr int kDppRowShr = 0x110, kDppWaveShr1 = 0x138, kDppBcast15 = 0x142,
+              kDppBcast31 = 0x143;
+
+template <int CTRL, int ROWS>
+__device__ __forceinline__ int32_t dpp(int32_t v) {
+    return __builtin_amdgcn_update_dpp(v, v, CTRL, ROWS, 0xf, false);
+}
+template <int CTRL, int ROWS>
+__device__ __forceinline__ int64_t dpp(int64_t v) {
+    const uint32_t lo = (uint32_t)dpp<CTRL, ROWS>((int32_t)(uint32_t)v);
+    const uint32_t hi = (uint32_t)dpp<CTRL, ROWS>((int32_t)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// the value of lane 63, in every lane
+__device__ __forceinline__ int32_t last_lane(int32_t v) {
+    return __builtin_amdgcn_readlane(v, 63);
+}
+__device__ __forceinline__ int64_t last_lane(int64_t v) {
+    const uint32_t lo = (uint32_t)last_lane((int32_t)(uint32_t)v);
+    const uint32_t hi = (uint32_t)last_lane((int32_t)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__device__ __forceinline__ int64_t sh_up(int64_t v, int o) {
+    return (int64_t)__shfl_up((unsigned long long)v, o, 64);
+}
+__device__ __forceinline__ int32_t sh_up(int32_t v, int o) { return __shfl_up(v, o, 64); }
+__device__ __forceinline__ int64_t sh_xor(int64_t v, int o) {
+    return (int64_t)__shfl_xor((unsigned long long)v, o, 64);
+}
+__device__ __forceinline__ int32_t sh_xor(int32_t v, int o) { return __shfl_xor(v, o, 64); }
+
+__device__ __forceinline__ int64_t ga_key(const Tup* p) {
+#ifdef KEY_8B
+    return p->key;
+#else
+    return (int64_t)reinterpret_cast<const int32_t*>(p)[1];
+#endif
+}
+
+// position of the highest set bit of a non-zero mask
+__device__ __forceinline__ uint32_t top_bit(uint64_t m) {
+    return 63u - (uint32_t)__clzll((long long)m);
+}
+
+// the lanes at or below this one
+__device__ __forceinline__ uint64_t lanemask_le() { return (2ull << lane_id()) - 1; }
+
+// The wave's chunk [cb, cb + GA_CHUNK) of `in`: keys and (PAY) payloads of the
+// elements inside the relation, and per round the ballot of the heads.
+template <bool PAY>
+__device__ __forceinline__ void ga_load(const Tup* __restrict__ in, uint64_t n, uint64_t cb,
+                                        uint32_t gsh, int64_t (&key)[GA_IPT],
+                                        MatVal (&pay)[GA_IPT], uint64_t (&hb)[GA_IPT]) {
+    const int lane = lane_id();
+#pragma unroll
+    for (int j = 0; j < GA_IPT; j++) {
+        const uint64_t gi = cb + 64 * j + lane;
+        key[j] = 0;
+        pay[j] = 0;
+        if (gi < n) {
+            if (PAY) {
+                const Tup t = in[gi];
+                key[j] = tup_key(t);
+                pay[j] = mat_payload(&t);
+            } else {
+                key[j] = ga_key(in + gi);
+            }
+        }
+    }
+    // the group in front of the chunk (the same address in every lane)
+    int64_t last = 0;
+    if (cb > 0 && cb < n) last = ga_key(in + cb - 1) >> gsh;
+#pragma unroll
+    for (int j = 0; j < GA_IPT; j++) {
+        const uint64_t gi = cb + 64 * j + lane;
+        const int64_t g = key[j] >> gsh;
+        int64_t pg = dpp<kDppWaveShr1, 0xf>(g);
+        if (lane == 0) pg = last;
+        hb[j] = __ballot(gi < n && (gi == 0 || g != pg));
+        last = last_lane(g);
+    }
+}
+
+template <int CTRL, int ROWS>
+__device__ __forceinline__ GAgg ga_dpp(const GAgg& v) {
+    return GAgg{dpp<CTRL, ROWS>(v.sum), dpp<CTRL, ROWS>(v.mn), dpp<CTRL, ROWS>(v.mx)};
+}
+
+// Inclusive segmented scan over the lanes of a wave: d = the lanes of this
+// lane's segment in front of it.  Four steps inside the rows of 16 lanes;
+// then rows 1 and 3 take the last lane of the row in front, and rows 2 and 3
+// lane 31, each lane only as far as its segment reaches.  (What lane 15, 31
+// or 47 holds by then covers its own segment, which is the taker's.)
+__device__ __forceinline__ GAgg ga_seg_scan(GAgg v, int d) {
+    const int lane = lane_id(), r = lane & 15;
+    GAgg y;
+    y = ga_dpp<kDppRowShr + 1, 0xf>(v);
+    if (r >= 1 && d >= 1) v = ga_comb(y, v);
+    y = ga_dpp<kDppRowShr + 2, 0xf>(v);
+    if (r >= 2 && d >= 2) v = ga_comb(y, v);
+    y = ga_dpp<kDppRowShr + 4, 0xf>(v);
+    if (r >= 4 && d >= 4) v = ga_comb(y, v);
+    y = ga_dpp<kDppRowShr + 8, 0xf>(v);
+    if (r >= 8 && d >= 8) v = ga_comb(y, v);
+    y = ga_dpp<kDppBcast15, 0xa>(v);
+    if ((lane & 16) && d > r) v = ga_comb(y, v);
+    y = ga_dpp<kDppBcast31, 0xc>(v);
+    if (lane >= 32 && d >= lane - 31) v = ga_comb(y, v);
+    return v;
+}
+
+struct GWave {  // what a wave leaves for the others of its tile
+    GCarry tail;
+    uint32_t heads;
+};
+
+// AGG 0: the tails' head positions alone (tail may be null: the count form),
+// 1: with their sums, 2: with minimum and maximum as well (what nobody asks
+// for is not computed: the scans are what the passes spend their time on).
+template <int AGG>
+__global__ void __launch_bounds__(GA_THREADS)
+k_group_count(const Tup* __restrict__ in, uint64_t n, uint32_t gsh, uint64_t* __restrict__ cnt,
+              GCarry* __restrict__ tail) {
+    __shared__ GWave L[GA_WAVES];
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const uint64_t cb = (uint64_t)blockIdx.x * GA_TILE + (uint64_t)w * GA_CHUNK;
+    int64_t key[GA_IPT];
+    MatVal pay[GA_IPT];
+    uint64_t hb[GA_IPT];
+    ga_load<AGG != 0>(in, n, cb, gsh, key, pay, hb);
+    uint32_t heads = 0;
+    uint64_t lstart = kNoHead;  // the chunk's last head
+#pragma unroll
+    for (int j = 0; j < GA_IPT; j++) {
+        heads += (uint32_t)__popcll(hb[j]);
+        if (hb[j]) lstart = cb + 64 * j + top_bit(hb[j]);
+    }
+    GAgg a = ga_none();
+    if (AGG) {
+#pragma unroll
+        for (int j = 0; j < GA_IPT; j++) {
+            const uint64_t gi = cb + 64 * j + lane;
+            // behind the last head, or everything (kNoHead is above every gi)
+            const bool in_tail = gi < n && (lstart == kNoHead || gi >= lstart);
+            if (in_tail) a = ga_comb(a, GAgg{(int64_t)pay[j], pay[j], pay[j]});
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+            a = ga_comb(a, GAgg{sh_xor(a.sum, o), sh_xor(a.mn, o), sh_xor(a.mx, o)});
+    }
+    if (lane == 0) {
+        L[w].tail = GCarry{a.sum, AGG == 2 ? (int64_t)a.mn : 0, AGG == 2 ? (int64_t)a.mx : 0,
+                           lstart};
+        L[w].heads = heads;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        GCarry t = gc_none();
+        uint64_t h = 0;
+#pragma unroll
+        for (int v = 0; v < GA_WAVES; v++) {
+            t = gc_comb(t, L[v].tail);
+            h += L[v].heads;
+        }
+        cnt[blockIdx.x] = h;
+        if (tail) tail[blockIdx.x] = t;
+    }
+}
+
+// ---- the carry step: a segmented scan of the tails over the tiles
+
+// inclusive scan of one GCarry per thread over the workgroup (GC_BLOCK
+// threads); *total = the whole workgroup's
+__device__ __forceinline__ GCarry gc_block_scan(GCarry v, GCarry* wl, GCarry* total) {
+    const int lane = lane_id(), wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        GCarry y;
+        y.sum = sh_up(v.sum, o);
+        y.mn = sh_up(v.mn, o);
+        y.mx = sh_up(v.mx, o);
+        y.start = (uint64_t)sh_up((int64_t)v.start, o);
+        if (lane >= o) v = gc_comb(y, v);
+    }
+    if (lane == 63) wl[wid] = v;
+    __syncthreads();
+    GCarry p = gc_none(), all = gc_none();
+#pragma unroll 1  // unrolled, the 16 entries are all loaded first (128 VGPRs and spills)
+    for (int x = 0; x < (int)(GC_BLOCK / 64); x++) {
+        if (x == wid) p = all;
+        all = gc_comb(all, wl[x]);
+    }
+    *total = all;
+    __syncthreads();  // wl is free again
+    return gc_comb(p, v);
+}
+
+// per GC_BLOCK tiles: their tails combined
+__global__ void __launch_bounds__(GC_BLOCK)
+k_group_carry_part(const GCarry* __restrict__ tail, uint64_t ntiles, GCarry* __restrict__ part) {
+    __shared__ GCarry wl[GC_BLOCK / 64];
+    const uint64_t t = (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x;
+    GCarry all;
+    gc_block_scan(t < ntiles ? tail[t] : gc_none(), wl, &all);
+    if (threadIdx.x == 0) part[blockIdx.x] = all;
+}
+
+// pexcl[b] = the parts in front of workgroup b combined (one workgroup)
+__global__ void __launch_bounds__(GC_BLOCK)
+k_group_carry_pscan(const GCarry* __restrict__ part, uint32_t nb, GCarry* __restrict__ pexcl) {
+    __shared__ GCarry wl[GC_BLOCK / 64];
+    GCarry run = gc_none();
+    if (threadIdx.x == 0) pexcl[0] = run;
+    for (uint32_t r0 = 0; r0 < nb; r0 += GC_BLOCK) {
+        const uint32_t b = r0 + threadIdx.x;
+        GCarry all;
+        const GCarry inc = gc_block_scan(b < nb ? part[b] : gc_none(), wl, &all);
+        if (b + 1 < nb) pexcl[b + 1] = gc_comb(run, inc);
+        run = gc_comb(run, all);
+    }
+}
+
+// carry[t] = the tails of all tiles in front of tile t combined
+__global__ void __launch_bounds__(GC_BLOCK)
+k_group_carry_down(const GCarry* __restrict__ tail, uint64_t ntiles,
+                   const GCarry* __restrict__ pexcl, GCarry* __restrict__ carry) {
+    __shared__ GCarry wl[GC_BLOCK / 64];
+    const uint64_t t = (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x;
+    GCarry all;
+    const GCarry inc = gc_block_scan(t < ntiles ? tail[t] : gc_none(), wl, &all);
+    const GCarry front = pexcl[blockIdx.x];
+    if (t == 0) carry[0] = front;
+    if (t + 1 < ntiles) carry[t + 1] = gc_comb(front, inc);
+}
+
+__device__ __forceinline__ void st_i64(int64_t* p, int64_t v) {
+#if SMJ_NT_STORES
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+
+// AGG 0: key, start and count alone, 1: the sum too, 2: minimum and maximum too
+template <int AGG>
+__global__ void __launch_bounds__(GA_THREADS)
+k_group_write(const Tup* __restrict__ in, uint64_t n, uint32_t gsh,
+              const uint64_t* __restrict__ base, const GCarry* __restrict__ carry,
+              GroupCols cols, uint64_t out_cap) {
+    __shared__ GWave L[GA_WAVES];
+    const uint64_t row0 = base[blockIdx.x];  // the heads in front of the tile
+    // the tile's first row is row0 - 1 (a group open at its first element)
+    // or row0: nothing below out_cap (uniform over the workgroup)
+    if (row0 > out_cap) return;
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const uint64_t cb = (uint64_t)blockIdx.x * GA_TILE + (uint64_t)w * GA_CHUNK;
+    const uint64_t le = lanemask_le();
+    int64_t key[GA_IPT];
+    MatVal pay[GA_IPT];
+    uint64_t hb[GA_IPT];
+    ga_load<AGG != 0>(in, n, cb, gsh, key, pay, hb);
+    // is the element behind the chunk a head (the relation's end counts)
+    const uint64_t ce = cb + GA_CHUNK;
+    bool next_head = ce == n;
+    if (ce < n) next_head = (ga_key(in + ce) >> gsh) != (ga_key(in + ce - 1) >> gsh);
+
+    GAgg x[GA_IPT];        // aggregate from the element's head, or the chunk's start, to it
+    uint64_t st[GA_IPT];   // that head's position; kNoHead: in front of the chunk
+    uint32_t hrank[GA_IPT];  // heads of the chunk at or before the element
+    GAgg run = ga_none();  // the open tail of the rounds so far
+    uint64_t rstart = kNoHead;
+    uint32_t heads = 0;
+#pragma unroll
+    for (int j = 0; j < GA_IPT; j++) {
+        const uint64_t rb = cb + 64 * j;
+        const uint64_t hm = hb[j] & le;  // the round's heads at or before this lane
+        const uint32_t seg = hm ? top_bit(hm) : 0;
+        if (AGG) {
+            GAgg v = rb + lane < n ? GAgg{(int64_t)pay[j], pay[j], pay[j]} : ga_none();
+            v = ga_seg_scan(v, lane - (int)seg);
+            if (!hm) v = ga_comb(run, v);
+            x[j] = v;
+            run = GAgg{last_lane(v.sum), last_lane(v.mn), last_lane(v.mx)};
+        }
+        st[j] = hm ? rb + seg : rstart;
+        if (hb[j]) rstart = rb + top_bit(hb[j]);
+        hrank[j] = heads + (uint32_t)__popcll(hm);
+        heads += (uint32_t)__popcll(hb[j]);
+    }
+    if (lane == 0) {
+        L[w].tail = GCarry{run.sum, AGG == 2 ? (int64_t)run.mn : 0, AGG == 2 ? (int64_t)run.mx : 0,
+                           rstart};
+        L[w].heads = heads;
+    }
+    __syncthreads();
+    // what comes in from the earlier tiles and the earlier waves of this one
+    GCarry inc = carry[blockIdx.x];
+    uint64_t row = row0;
+#pragma unroll
+    for (int v = 0; v < GA_WAVES - 1; v++) {
+        if (v < w) {
+            inc = gc_comb(inc, L[v].tail);
+            row += L[v].heads;
+        }
+    }
+    const GAgg ia{inc.sum, (MatVal)inc.mn, (MatVal)inc.mx};
+#pragma unroll
+    for (int j = 0; j < GA_IPT; j++) {
+        const uint64_t rb = cb + 64 * j;
+        const uint64_t gi = rb + lane;
+        // the heads one element on: those of this round, then the first of
+        // the next one; position n counts as a head
+        uint64_t nx = j + 1 < GA_IPT ? hb[j + 1 < GA_IPT ? j + 1 : j] : (uint64_t)next_head;
+        if (rb + 64 == n) nx = 1;
+        uint64_t eb = (hb[j] >> 1) | (nx << 63);
+        if (n > rb && n < rb + 64) eb |= 1ull << (n - rb - 1);
+        if (!((eb >> lane) & 1) || gi >= n) continue;
+        const uint64_t r = row + hrank[j] - 1;  // element 0 is a head: no row below 0
+        if (r >= out_cap) continue;
+        const bool far = st[j] == kNoHead;
+        const uint64_t s = far ? inc.start : st[j];
+        if (cols.key) {
+            int64_t k = key[j];
+            if (gsh != 0 && s < gi) k = ga_key(in + s);  // s <= gi < n
+            st_val(cols.key + r, (MatVal)k);
+        }
+        if (cols.start) st_i64(cols.start + r, (int64_t)s);
+        if (cols.count) st_i64(cols.count + r, (int64_t)(gi - s + 1));
+        if (AGG) {
+            const GAgg a = far ? ga_comb(ia, x[j]) : x[j];
+            if (cols.sum) st_i64(cols.sum + r, a.sum);
+            if (AGG == 2 && cols.mn) st_val(cols.mn + r, a.mn);
+            if (AGG == 2 && cols.mx) st_val(cols.mx + r, a.mx);
+        }
+    }
+}
+
+// the tiles' heads added to *total, one atomic per 1024 tiles (k_band_total's
+// reduction)
+constexpr uint32_t GT_BLOCK = 1024;
+
+__global__ void __launch_bounds__(GT_BLOCK)
+k_group_total(const uint64_t* __restrict__ cnt, uint64_t ntiles, unsigned long long* total) {
+    __shared__ uint64_t ws[GT_BLOCK / 64];
+    const uint64_t t = (uint64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
+    const uint64_t c = wave_sum(t < ntiles ? cnt[t] : 0);
+    if (lane_id() == 0) ws[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t a = 0;
+        for (uint32_t w = 0; w < GT_BLOCK / 64; w++) a += ws[w];
+        if (a) atomicAdd(total, (unsigned long long)a);
+    }
+}
+
+struct GroupTab {
+    uint64_t ntiles;
+    uint32_t nb;  // workgroups of the carry step
+    uint64_t *cnt, *base, *ibase, *tot;
+    GCarry *tail, *carry, *part, *pexcl;
+};
+
+static GroupTab group_tab(Workspace* ws, uint64_t n) {
+    GroupTab g;
+    g.ntiles = (n + GA_TILE - 1) / GA_TILE;
+    g.nb = (uint32_t)((g.ntiles + GC_BLOCK - 1) / GC_BLOCK);
+    const size_t words = 3 * g.ntiles + 2 + ((3 * g.ntiles) & 1);  // the GCarry tables 16-aligned
+    char* tab = (char*)ws->scratch(
+        "group_tab", words * 8 + (2 * g.ntiles + 2 * (size_t)g.nb) * sizeof(GCarry));
+    g.cnt = (uint64_t*)tab;
+    g.base = g.cnt + g.ntiles;
+    g.ibase = g.base + g.ntiles;
+    g.tot = g.ibase + g.ntiles;
+    g.tail = (GCarry*)(tab + words * 8);
+    g.carry = g.tail + g.ntiles;
+    g.part = g.carry + g.ntiles;
+    g.pexcl = g.part + g.nb;
+    return g;
+}
+
+template <int AGG>
+static void group_count_pass(Workspace* ws, const Tup* in, uint64_t n, uint32_t gsh,
+                             const GroupTab& g, bool tails, hipStream_t st) {
+    TraceScope ts(ws, "k_group_count", st);
+    hipLaunchKernelGGL(k_group_count<AGG>, dim3((uint32_t)g.ntiles), dim3(GA_THREADS), 0, st, in,
+                       n, gsh, g.cnt, tails ? g.tail : nullptr);
+    SMJ_CHECK(hipGetLastError());
+}
+
+uint64_t group_aggregate(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift,
+                         void* key_out, int64_t* start_out, int64_t* count_out,
+                         int64_t* sum_out, void* min_out, void* max_out, uint64_t out_cap,
+                         hipStream_t st) {
+    if (n == 0) return 0;
+    const GroupCols cols{(MatVal*)key_out, start_out, count_out, sum_out, (MatVal*)min_out,
+                         (MatVal*)max_out};
+    const int agg = (cols.mn || cols.mx) ? 2 : cols.sum ? 1 : 0;
+    const bool rows = out_cap && (agg || cols.key || cols.start || cols.count);
+    const GroupTab g = group_tab(ws, n);
+    if (rows && agg == 2) group_count_pass<2>(ws, in, n, group_shift, g, true, st);
+    else if (rows && agg == 1) group_count_pass<1>(ws, in, n, group_shift, g, true, st);
+    else group_count_pass<0>(ws, in, n, group_shift, g, rows, st);
+    mat_scan(ws, g.cnt, g.ntiles, g.base, g.ibase, g.tot, st);
+    if (rows) {
+        {
+            TraceScope ts(ws, "k_group_carry", st);
+            hipLaunchKernelGGL(k_group_carry_part, dim3(g.nb), dim3(GC_BLOCK), 0, st, g.tail,
+                               g.ntiles, g.part);
+            SMJ_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_group_carry_pscan, dim3(1), dim3(GC_BLOCK), 0, st, g.part, g.nb,
+                               g.pexcl);
+            SMJ_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_group_carry_down, dim3(g.nb), dim3(GC_BLOCK), 0, st, g.tail,
+                               g.ntiles, g.pexcl, g.carry);
+            SMJ_CHECK(hipGetLastError());
+        }
+        // every tile is launched: those whose rows lie at out_cap and above
+        // leave at once, so the launch needs no count on the host
+        TraceScope ts(ws, "k_group_write", st);
+        const dim3 grid((uint32_t)g.ntiles), block(GA_THREADS);
+        if (agg == 2)
+            hipLaunchKernelGGL(k_group_write<2>, grid, block, 0, st, in, n, group_shift, g.base,
+                               g.carry, cols, out_cap);
+        else if (agg == 1)
+            hipLaunchKernelGGL(k_group_write<1>, grid, block, 0, st, in, n, group_shift, g.base,
+                               g.carry, cols, out_cap);
+        else
+            hipLaunchKernelGGL(k_group_write<0>, grid, block, 0, st, in, n, group_shift, g.base,
+                               g.carry, cols, out_cap);
+        SMJ_CHECK(hipGetLastError());
+    }
+    uint64_t* h = (uint64_t*)ws->host_pinned("group_tot_h", 16);
+    SMJ_CHECK(hipMemcpyAsync(h, g.tot, 16, hipMemcpyDeviceToHost, st));
+    SMJ_CHECK(hipStreamSynchronize(st));
+    return h[0];
+}
+
+void group_count(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift,
+                 unsigned long long* groups_dev, hipStream_t st) {
+    if (n == 0) return;
+    const GroupTab g = group_tab(ws, n);
+    group_count_pass<0>(ws, in, n, group_shift, g, false, st);
+    TraceScope ts(ws, "k_group_total", st);
+    hipLaunchKernelGGL(k_group_total, dim3((uint32_t)((g.ntiles + GT_BLOCK - 1) / GT_BLOCK)),
+                       dim3(GT_BLOCK), 0, st, g.cnt, g.ntiles, groups_dev);
+    SMJ_CHECK(hipGetLastError());
+}
+
+}  // namespace smj

@@ -477,6 +477,23 @@ void asof_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t 
                int64_t* r_index_out, void* r_payload_out, void* r_key_out,
                unsigned long long* matched_dev, hipStream_t st);
 
+// ---- groupagg.hip : grouped aggregation of a sorted relation (smj.h
+// smj_dev_group_aggregate)
+// One row per maximal run of equal key >> group_shift (0..63), in input
+// order: the run's first key, its start and length, and the sum (int64,
+// wrapping), minimum and maximum of its payloads, as columns of the ABI's
+// intkey_t / int64 / value_t (each may be null).  Writes the first
+// min(groups, out_cap) rows and returns the number of groups (synchronises
+// `st` once; n == 0 returns 0 at once).
+uint64_t group_aggregate(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift,
+                         void* key_out, int64_t* start_out, int64_t* count_out,
+                         int64_t* sum_out, void* min_out, void* max_out, uint64_t out_cap,
+                         hipStream_t st);
+// its number of groups, added to *groups_dev (stream-ordered, no synchronisation)
+void group_count(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift,
+                 unsigned long long* groups_dev, hipStream_t st);
+uint32_t group_tile();  // elements of `in` a workgroup of its kernels handles
+
 // ---- datagen.hip
 void gen_pk(Tup* out, uint64_t n, uint64_t first, uint64_t total,
             uint64_t seed, hipStream_t st);

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from builtins import min as builtins_min  # dev_group_aggregate has a `min` column
 
 import numpy as np
 
@@ -72,6 +73,7 @@ DEVICE_SYMBOLS = [
     "smj_dev_partition_range_shards", "smj_tilepass_occupancy",
     "smj_dev_join_pairs", "smj_dev_semi_join",
     "smj_dev_band_join", "smj_dev_band_join_count", "smj_dev_asof_join",
+    "smj_dev_group_aggregate", "smj_dev_group_count", "smj_group_tile",
 ]
 # smj_dev_asof_join's mode (SMJ_ASOF_* in smj.h)
 ASOF_DIRECTIONS = {"backward": 0, "forward": 1, "nearest": 2}
@@ -290,6 +292,10 @@ class Library:
             "smj_dev_band_join_count": (None, [_P, _P, _U64, _P, _U64, _I64, _I64, _P, _P]),
             "smj_dev_asof_join": (None, [_P, _P, _U64, _P, _U64, _U32, _U64, _U32, _P, _P, _P,
                                          _P, _P]),
+            "smj_dev_group_aggregate": (_U64, [_P, _P, _U64, _U32, _P, _P, _P, _P, _P, _P,
+                                               _U64, _P]),
+            "smj_dev_group_count": (None, [_P, _P, _U64, _U32, _P, _P]),
+            "smj_group_tile": (_U32, []),
             "smj_selfcheck_lds_order": (_U64, [_P, _P]),
             "smj_context_workspace": (_P, []),
             "smj_dev_gen_nonunique": (None, [_P, _P, _U64, _U64, _U64, _I64, _U32, _U64, _P]),
@@ -903,6 +909,68 @@ class Library:
             self.dev_asof_join(sR, sS, direction, strict, tolerance, group_shift, idx, *cols)
         out = (sS[:, 0].contiguous(), cols[0], idx >= 0)
         return out + (sS[:, 1].contiguous(), cols[1]) if with_keys else out
+
+    @staticmethod
+    def _group_shift(group_shift):
+        group_shift = int(group_shift)
+        assert 0 <= group_shift <= 63, "group_shift is 0 (by key) to 63"
+        return group_shift
+
+    def _group_column(self, t, what, dtype=None):
+        dt = dtype or (torch.int32 if self.width == 8 else torch.int64)
+        assert t.dim() == 1 and t.dtype == dt and t.is_contiguous() and t.is_cuda, what
+        return t
+
+    def dev_group_aggregate(self, sorted, group_shift=0, key=None, start=None, count=None,
+                            sum=None, min=None, max=None):
+        """Grouped aggregation (smj_dev_group_aggregate): one row per maximal
+        run of equal (key >> group_shift) in `sorted`, in input order -- on a
+        sorted relation, GROUP BY.  Each column given gets the first rows, as
+        many as the shortest of them holds: key (the run's first key) and min
+        / max (of its payloads) in the payload dtype, start (its position),
+        count (its length) and sum (of its payloads, wrapping) in int64.
+        Returns the number of groups; no columns: count only.  Synchronises
+        the current stream once."""
+        gsh = self._group_shift(group_shift)
+        cols = [(key, "key", None), (start, "start", torch.int64), (count, "count", torch.int64),
+                (sum, "sum", torch.int64), (min, "min", None), (max, "max", None)]
+        given = [self._group_column(t, what, dt) for t, what, dt in cols if t is not None]
+        cap = builtins_min(t.shape[0] for t in given) if given else 0
+        ptrs = [t.data_ptr() if t is not None and cap else None for t, _, _ in cols]
+        return int(self.lib.smj_dev_group_aggregate(
+            self.ws, sorted.data_ptr(), sorted.shape[0], gsh, *ptrs, cap, self.stream_ptr()))
+
+    def dev_group_count(self, sorted, group_shift, groups):
+        """smj_dev_group_count: the number of groups added to groups[0] (int64
+        device tensor), stream-ordered."""
+        gsh = self._group_shift(group_shift)
+        self._group_column(groups, "groups", torch.int64)
+        assert groups.shape[0] >= 1, "groups holds the counter"
+        self.lib.smj_dev_group_count(self.ws, sorted.data_ptr(), sorted.shape[0], gsh,
+                                     groups.data_ptr(), self.stream_ptr())
+
+    def group_tile(self):
+        """Elements one workgroup of the group kernels handles (a host call)."""
+        return int(self.lib.smj_group_tile())
+
+    def group_by(self, T, group_shift=0):
+        """GROUP BY (key >> group_shift) of an unsorted device relation in one
+        call: sorts it (dev_sort) into a temporary, counts the groups and
+        returns exactly sized 1-D tensors (keys, starts, counts, sums, mins,
+        maxs) on the current stream, in key order; starts are positions in
+        the sorted relation."""
+        dt = torch.int32 if self.width == 8 else torch.int64
+        n, groups = T.shape[0], 0
+        if n:
+            sT = self.empty(n)
+            self.dev_sort(T, sT)
+            groups = self.dev_group_aggregate(sT, group_shift)
+        cols = [torch.empty(groups, dtype=d, device=T.device)
+                for d in (dt, torch.int64, torch.int64, torch.int64, dt, dt)]
+        if groups:
+            got = self.dev_group_aggregate(sT, group_shift, *cols)
+            assert got == groups, (got, groups)
+        return tuple(cols)
 
     def dev_join(self, R, S, sortedR, sortedS, count, fanout_bits=10,
                  key_min=1, key_max=0):

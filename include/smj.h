@@ -728,6 +728,55 @@ void smj_dev_asof_join(smj_workspace * ws, const tuple_t * sortedR, uint64_t nR,
                        unsigned long long * matched_dev /* may be NULL */,
                        smj_stream_t stream);
 
+/* Grouped aggregation of a sorted relation: one output row per group, with
+ * the group's first key, where it starts, how many tuples it holds and the
+ * sum, minimum and maximum of their payloads (sort-based GROUP BY; the
+ * library's own).  Two group tables give the per-key join cardinality
+ * count_R[k] * count_S[k] without a join, and start/count are CSR offsets into
+ * the sorted relation.  Total: there is no undefined input.
+ * Group: a maximal run of consecutive tuples with equal key >> group_shift,
+ *   an arithmetic shift of the key widened to int64, the group_shift of
+ *   smj_dev_asof_join.  0 groups by key; values above 63 abort with a
+ *   message.  On a relation with non-decreasing keys this is GROUP BY; on any
+ *   other input it is the run-length form: keys 1,1,2,1 give three groups.
+ *   Only the key order matters: the payloads of a run may come in any order
+ *   (minimum and maximum are not taken from its first and last tuple).
+ * Rows: row g belongs to the g-th group in input order.  key_out[g] is the
+ *   key of the group's first tuple, start_out[g] that tuple's position in
+ *   `sorted`, count_out[g] the number of tuples, sum_out[g] the sum of the
+ *   payloads as int64 modulo 2^64 (two's complement wrap-around; the 8-byte
+ *   library sign-extends its int32 payloads first), min_out[g] and max_out[g]
+ *   their signed minimum and maximum.
+ * Output: the first min(groups, out_cap) rows of every non-NULL column are
+ *   written, everything else is left alone, and the number of groups is
+ *   returned.  out_cap = 0, or all columns NULL, only counts.  Synchronises
+ *   `stream` once, like smj_dev_band_join.
+ * Empty call: n == 0 returns 0, launches nothing and does not synchronise.
+ * Buffers: the input is left untouched; the outputs must not overlap it.
+ *   Alignment as for the rest of the device API: any tuple-granular slice of a
+ *   hipMalloc buffer (for the 8-byte library also one at an address that is
+ *   8 mod 16), columns aligned to their element. */
+uint64_t smj_dev_group_aggregate(smj_workspace * ws, const tuple_t * sorted, uint64_t n,
+                                 uint32_t group_shift,
+                                 intkey_t * key_out   /* may be NULL */,
+                                 int64_t *  start_out /* may be NULL */,
+                                 int64_t *  count_out /* may be NULL */,
+                                 int64_t *  sum_out   /* may be NULL */,
+                                 value_t *  min_out   /* may be NULL */,
+                                 value_t *  max_out   /* may be NULL */,
+                                 uint64_t out_cap, smj_stream_t stream);
+
+/* Its number of groups only, ADDED to *groups_dev (device), stream-ordered
+ * like smj_dev_band_join_count: no host synchronisation (the workspace's
+ * tables grow on a first call).  The same groups; n == 0 adds nothing. */
+void smj_dev_group_count(smj_workspace * ws, const tuple_t * sorted, uint64_t n,
+                         uint32_t group_shift, unsigned long long * groups_dev,
+                         smj_stream_t stream);
+
+/* Elements of `sorted` one workgroup of the group kernels handles (for tests;
+ * a host call, no device needed). */
+uint32_t smj_group_tile(void);
+
 /* The m-way join on one device.  R and S are left untouched; sortedR/sortedS
  * (n tuples each) receive the fully sorted relations; the match count is
  * written to *count_dev.  key_min <= key_max is an optional hint of the key
