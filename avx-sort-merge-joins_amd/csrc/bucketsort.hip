@@ -2163,10 +2163,11 @@ k_skew_check(SkewArgs K) {
 // The queued groups [0, no): device skew kernels, then whatever they could
 // not finish (inexact digits, equal-key runs out of payload order) through
 // the segmented merge sort and the merge-join count.  hdst[r * nb + b] is
-// bucket b's output start.
+// bucket b's output start.  stats receives what was done (smj_skew_stats).
 template <class Lay>
 static void skew_path(Workspace* ws, const GroupArgs& G, OvfEntry* ovf, uint32_t no,
-                      const uint64_t* hdst, uint32_t nb, hipStream_t st) {
+                      const uint64_t* hdst, uint32_t nb, hipStream_t st,
+                      Workspace::SkewStats& stats) {
     const int nrel = G.nrel;
     // pinned host copies (a pageable destination makes each copy a staged,
     // blocking transfer)
@@ -2178,6 +2179,7 @@ static void skew_path(Workspace* ws, const GroupArgs& G, OvfEntry* ovf, uint32_t
     std::vector<uint4> items;
     for (uint32_t i = 0; i < no; i++) {
         const uint32_t m = std::max(he[i].nr[0], nrel > 1 ? he[i].nr[1] : 0u);
+        if (m == 0) stats.empty++;
         if (m <= kSkewSmall) {
             small.push_back(i);
             continue;
@@ -2195,6 +2197,10 @@ static void skew_path(Workspace* ws, const GroupArgs& G, OvfEntry* ovf, uint32_t
         }
     }
     const size_t nl = large.size();
+    stats.queued = no;
+    stats.small = (uint32_t)small.size();
+    stats.large = (uint32_t)nl;
+    stats.items = (uint32_t)items.size();
     const size_t lbytes = (small.size() + 2 * nl) * 4;
     const size_t ibytes = items.size() * sizeof(uint4);
     unsigned char* hbuf = (unsigned char*)ws->host_pinned("sk_h", lbytes + ibytes + 16);
@@ -2246,8 +2252,12 @@ static void skew_path(Workspace* ws, const GroupArgs& G, OvfEntry* ovf, uint32_t
     ws->wait_stream(st);
     // what the device could not finish
     std::vector<uint32_t> rest;
-    for (uint32_t i = 0; i < no; i++)
+    for (uint32_t i = 0; i < no; i++) {
+        if ((flags[i] & 1u) || G.plan.s3 != 0) stats.inexact++;
+        if (flags[i] & 2u) stats.unordered++;
         if (flags[i] != 0 || G.plan.s3 != 0) rest.push_back(i);
+    }
+    stats.resorted = (uint32_t)rest.size();
     if (rest.empty()) return;
     for (int r = 0; r < nrel; r++) {
         std::vector<uint64_t> so, sl;
@@ -2267,6 +2277,7 @@ static void skew_path(Workspace* ws, const GroupArgs& G, OvfEntry* ovf, uint32_t
             nr.push_back(he[i].nr[0]);
             ns.push_back(he[i].nr[1]);
         }
+        stats.recounted = (uint32_t)rp.size();
         merge_join_count_batch(ws, rp.data(), nr.data(), sp.data(), ns.data(),
                                (uint32_t)rp.size(), G.count_dev, st);
     }
@@ -2691,12 +2702,14 @@ static bool bucket_sort_nosync(Workspace* ws, const BucketSortArgs& a, hipStream
         return true;  // the group pass comes with a later call
     }
     if (a.ev_bucket) SMJ_CHECK(hipEventRecord(a.ev_bucket, st));
+    Workspace::SkewStats stats;  // kept on ws once this pass completes
     {
         const uint32_t maxwg =
             (G.pair ? gs_wg_per_cu<W, true>() : gs_wg_per_cu<W, false>()) * 256;
         const uint32_t nwg = groupsort_grid(ngroups, maxwg, G.per);
         TraceScope ts(ws, "k_groupsort", st);
-        launch_groupsort<LayG>(ws, group_tpl(nmax, nb, a.nseg, tsz), nwg, st, G);
+        stats.tpl = (uint32_t)group_tpl(nmax, nb, a.nseg, tsz);
+        launch_groupsort<LayG>(ws, (int)stats.tpl, nwg, st, G);
     }
     SMJ_CHECK(hipGetLastError());
     if (a.ev_ovf) SMJ_CHECK(hipEventRecord(a.ev_ovf, st));
@@ -2722,7 +2735,11 @@ static bool bucket_sort_nosync(Workspace* ws, const BucketSortArgs& a, hipStream
     // tile and group passes exited at once on the latter two
     if (h[0] || h[1]) return false;
     const uint32_t no = h[2];
-    if (no == 0) return true;
+    if (no == 0) {
+        ws->skew = stats;
+        ws->skew_valid = true;
+        return true;
+    }
     if (no > ovf_cap) {
         fprintf(stderr, "[ERROR] smj: overflow table too small\n");
         abort();
@@ -2731,7 +2748,9 @@ static bool bucket_sort_nosync(Workspace* ws, const BucketSortArgs& a, hipStream
     for (int r = 0; r < nrel; r++)
         SMJ_CHECK(hipMemcpyAsync(hdst + (size_t)r * nb, ostart[r], (size_t)nb * 8,
                                  hipMemcpyDeviceToHost, st));
-    skew_path<LayG>(ws, G, ovf, no, hdst, nb, st);
+    skew_path<LayG>(ws, G, ovf, no, hdst, nb, st, stats);
+    ws->skew = stats;
+    ws->skew_valid = true;
     SMJ_CHECK(hipGetLastError());
     return true;
 }
@@ -2907,6 +2926,7 @@ bool bucket_sort(Workspace* ws, const BucketSortArgs& a, hipStream_t st) {
     if (a.ev_bucket) SMJ_CHECK(hipEventRecord(a.ev_bucket, st));
     G.g_begin = 0;
     G.g_end = nb * nb2;
+    Workspace::SkewStats stats;  // kept on ws once this pass completes
     {
         // persistent: gs_wg_per_cu workgroups per CU, consecutive groups each
         const uint32_t ng = G.g_end - G.g_begin;
@@ -2914,7 +2934,8 @@ bool bucket_sort(Workspace* ws, const BucketSortArgs& a, hipStream_t st) {
         const uint32_t nwg = groupsort_grid(ng, maxwg, G.per);
         TraceScope ts(ws, "k_groupsort", st);
         const uint64_t nmax = nrel > 1 && a.n[1] > a.n[0] ? a.n[1] : a.n[0];
-        launch_groupsort<LayTup>(ws, group_tpl(nmax, nb, nseg, tsz), nwg, st, G);
+        stats.tpl = (uint32_t)group_tpl(nmax, nb, nseg, tsz);
+        launch_groupsort<LayTup>(ws, (int)stats.tpl, nwg, st, G);
     }
     SMJ_CHECK(hipGetLastError());
     if (a.ev_ovf) SMJ_CHECK(hipEventRecord(a.ev_ovf, st));
@@ -2924,12 +2945,18 @@ bool bucket_sort(Workspace* ws, const BucketSortArgs& a, hipStream_t st) {
     SMJ_CHECK(hipMemcpyAsync(h_novf, novf, 4, hipMemcpyDeviceToHost, st));
     ws->wait_stream(st);
     const uint32_t no = *h_novf;
-    if (no == 0) return true;
+    if (no == 0) {
+        ws->skew = stats;
+        ws->skew_valid = true;
+        return true;
+    }
     if (no > ovf_cap) {
         fprintf(stderr, "[ERROR] smj: overflow table too small\n");
         abort();
     }
-    skew_path<LayTup>(ws, G, ovf, no, hdst, nb, st);
+    skew_path<LayTup>(ws, G, ovf, no, hdst, nb, st, stats);
+    ws->skew = stats;
+    ws->skew_valid = true;
     SMJ_CHECK(hipGetLastError());
     return true;
 }

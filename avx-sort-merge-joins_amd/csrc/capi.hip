@@ -1774,6 +1774,15 @@ int smj_workspace_last_layout(smj_workspace* ws) {
     return ((Workspace*)(ws ? ws : smj_context_workspace()))->last_layout;
 }
 
+int smj_workspace_skew_stats(smj_workspace* ws, smj_skew_stats* out) {
+    const Workspace* w = (Workspace*)(ws ? ws : smj_context_workspace());
+    if (!w->skew_valid) return -1;
+    const Workspace::SkewStats& s = w->skew;
+    *out = smj_skew_stats{s.tpl,   s.queued,  s.empty,     s.small,    s.large,
+                          s.items, s.inexact, s.unordered, s.resorted, s.recounted};
+    return 0;
+}
+
 int smj_tilepass_occupancy(int layout, uint32_t d2_bits) {
     if (layout != SMJ_LAYOUT_USED_P48 && layout != SMJ_LAYOUT_USED_P32) return -1;
     return tilepass_occupancy(layout == SMJ_LAYOUT_USED_P32, d2_bits);

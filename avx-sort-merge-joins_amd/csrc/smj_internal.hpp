@@ -102,6 +102,15 @@ struct Workspace {
         return *victim;
     }
     int last_layout = -1;  // smj_workspace_last_layout (SMJ_LAYOUT_USED_*)
+    // smj_workspace_skew_stats: what the skew path of the last completed
+    // bucket pass did, in the order of smj_skew_stats (smj.h); host values the
+    // pass holds anyway
+    struct SkewStats {
+        uint32_t tpl = 0, queued = 0, empty = 0, small = 0, large = 0, items = 0, inexact = 0,
+                 unordered = 0, resorted = 0, recounted = 0;
+    };
+    SkewStats skew;
+    bool skew_valid = false;
     std::map<std::string, std::pair<void*, size_t>> bufs;
     std::map<std::string, std::pair<void*, size_t>> pinned;
     // the k-way merge's run table as last uploaded, and where (a repeated

@@ -74,6 +74,7 @@ DEVICE_SYMBOLS = [
     "smj_dev_join_pairs", "smj_dev_semi_join",
     "smj_dev_band_join", "smj_dev_band_join_count", "smj_dev_asof_join",
     "smj_dev_group_aggregate", "smj_dev_group_count", "smj_group_tile",
+    "smj_workspace_skew_stats",
 ]
 # smj_dev_asof_join's mode (SMJ_ASOF_* in smj.h)
 ASOF_DIRECTIONS = {"backward": 0, "forward": 1, "nearest": 2}
@@ -131,6 +132,9 @@ LAYOUT_NO_P48, LAYOUT_NO_PACKED, LAYOUT_NO_SAMPLED, LAYOUT_SAMPLE_PLAN = 1, 2, 4
 LAYOUT_NO_P32, LAYOUT_NO_P96 = 16, 32
 # smj_workspace_last_layout values
 LAYOUTS_USED = ("tuples", "words", "p48", "p32", "p96")
+# the fields of smj_skew_stats (smj.h), all uint32_t
+SKEW_STATS = ("tpl", "queued", "empty", "small", "large", "items", "inexact", "unordered",
+              "resorted", "recounted")
 # smj_mgpu_join flags (include/smj.h)
 MG_COPY, MG_NOPLANES, MG_ONECALL, MG_SAMPLED, MG_EXACT = 1, 2, 4, 8, 16
 MG_LAYOUTS = ("tuples", "words", "planes")
@@ -322,6 +326,7 @@ class Library:
             "smj_inregister_sort_keyval32": (None, [_P, _P, _U64]),
             "smj_workspace_set_layouts": (None, [_P, _U32]),
             "smj_workspace_last_layout": (C.c_int, [_P]),
+            "smj_workspace_skew_stats": (C.c_int, [_P, _P]),
             "smj_tilepass_occupancy": (C.c_int, [C.c_int, _U32]),
             "smj_trace_enable": (None, [_P, C.c_int]),
             "smj_trace_reset": (None, [_P]),
@@ -639,6 +644,15 @@ class Library:
             return "unknown"
         k = f(None if api else self.ws)
         return LAYOUTS_USED[k] if k >= 0 else "none"
+
+    def skew_stats(self):
+        """smj_workspace_skew_stats as a dict (keys SKEW_STATS): what the skew
+        path of the last completed bucket pass on this Library's workspace
+        did; None before the first."""
+        out = (C.c_uint32 * len(SKEW_STATS))()
+        if self.lib.smj_workspace_skew_stats(self.ws, out) != 0:
+            return None
+        return dict(zip(SKEW_STATS, (int(v) for v in out)))
 
     def tilepass_occupancy(self, layout: str = "p48", d2_bits: int = 10) -> int:
         """smj_tilepass_occupancy: workgroups of the tile-pass kernel of

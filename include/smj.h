@@ -558,6 +558,28 @@ void smj_workspace_set_layouts(smj_workspace * ws, uint32_t off);
 #define SMJ_LAYOUT_USED_P32    3
 #define SMJ_LAYOUT_USED_P96    4
 int smj_workspace_last_layout(smj_workspace * ws);
+/* What became of the groups that the group pass could not finish in LDS and
+ * queued for the skew path, in the last bucket pass (the tile and group passes
+ * of a device sort or join) that completed on `ws` (NULL: the calling
+ * thread's workspace).  An attempt that is repeated in another layout or with
+ * another plan (region overflow, payloads that do not pack, a key outside a
+ * guessed range) leaves the record as it was.  Host values the pass holds
+ * anyway: no copy and no synchronisation is added for them.  For tests.
+ * Returns 0, or -1 (and leaves *out) before the first such pass. */
+typedef struct smj_skew_stats {
+    uint32_t tpl;        /* tile runs a lane of the last group pass took: 2 or 4 */
+    uint32_t queued;     /* groups in the queue (0: the skew path did not run) */
+    uint32_t empty;      /* ... with no tuple in either relation */
+    uint32_t small;      /* ... taken by one workgroup each */
+    uint32_t large;      /* ... taken by the split kernels */
+    uint32_t items;      /* work items of the large ones */
+    uint32_t inexact;    /* ... whose digits did not order the keys (every one
+                            when the plan has key bits below the last digit) */
+    uint32_t unordered;  /* ... with equal keys out of payload order */
+    uint32_t resorted;   /* groups handed to the segmented merge sort */
+    uint32_t recounted;  /* pairs handed to the batched merge-join count */
+} smj_skew_stats;
+int smj_workspace_skew_stats(smj_workspace * ws, smj_skew_stats * out);
 /* Workgroups of the tile-pass kernel that intermediate layout `layout`
  * (SMJ_LAYOUT_USED_P48 or _P32) takes which the runtime places on one compute
  * unit (hipOccupancyMaxActiveBlocksPerMultiprocessor) at the dynamic LDS size

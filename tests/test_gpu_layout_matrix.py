@@ -231,14 +231,21 @@ def relation(width, keys, pay):
 
 def input_key(case, width):
     """What the input relations of a case depend on."""
-    return (width, case.kind, case.nR, case.nS, case.keys.tag, case.pay, case.pay_bits(width))
+    return (width, case.kind, case.nR, case.nS, case.keys.tag, case.pay, case.pay_bits(width),
+            getattr(case, "fix", None))
 
 
 def build(case, width):
     """The input relations of a case: [R, S] or [R]."""
     ks = case.keys(_seed(case.keys.tag, *case.ns), width, *case.ns)
     rng = _seed(case.pay, case.pay_bits(width) or 0, width, *case.ns)
-    return [relation(width, k, payloads(case, width, len(k), rng)) for k in ks]
+    rels = [relation(width, k, payloads(case, width, len(k), rng)) for k in ks]
+    if getattr(case, "fix", None) == "ident":
+        # (test_gpu_skew_matrix) the tuples of a key all alike: its first payload
+        for t in rels:
+            _, first, inv = np.unique(t["key"], return_index=True, return_inverse=True)
+            t["payload"] = t["payload"][first][inv]
+    return rels
 
 
 # ---- key generators: f(rng, width, nR[, nS]) -> key arrays ------------------
@@ -704,12 +711,13 @@ def _check_out(lib, buf, view, want, what):
     assert np.array_equal(lib.to_host(view), want), f"{what}: sorted relation differs"
 
 
-def run_case(lib, orc, case, placement=None):
+def run_case(lib, orc, case, placement=None, check=None):
     """The case (a join or a sort), twice on one fresh workspace, with all the
     checks of the module docstring.  placement: the tuple offsets of the
     buffers in their arenas, (R_in, S_in, R_out, S_out) for a join, (in, out)
     for a sort, or ("inplace", off) for a sort whose output is its input;
-    None: all 0."""
+    None: all 0.  check(case, width, call, lib.skew_stats(), ran) is called
+    after the checks of every call (ran: the traced kernels that ran)."""
     import torch
     from placement import check_guards
     width = lib.width
@@ -762,14 +770,16 @@ def run_case(lib, orc, case, placement=None):
             assert seen[1] == case.exact(width, call), f"{what}: exact partition ran: {seen[1]}"
             if case.skew:
                 assert seen[2], f"{what}: no skew kernel ran ({sorted(ran)})"
+            if check is not None:
+                check(case, width, call, lib.skew_stats(), ran)
     finally:
         lib.set_layouts(0)
         lib.reset_workspace()
     return "ran"
 
 
-def run_cases(libs, oracles, width, cases, placement=None):
-    done = [run_case(libs[width], oracles[width], c, placement) for c in cases]
+def run_cases(libs, oracles, width, cases, placement=None, check=None):
+    done = [run_case(libs[width], oracles[width], c, placement, check) for c in cases]
     if "ran" not in done:
         pytest.skip(cases[0].why)
 
