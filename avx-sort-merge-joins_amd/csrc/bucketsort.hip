@@ -2764,10 +2764,11 @@ static int tilepass_blocks(K kernel, size_t lds) {
     SMJ_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, TP_THREADS, lds));
     return n;
 }
-int tilepass_occupancy(bool p32, uint32_t d2) {
-    if (d2 > kMaxD2) return -1;
+int tilepass_occupancy(Layout lay, uint32_t d2) {
+    if ((lay != Layout::P48 && lay != Layout::P32) || d2 > kMaxD2) return -1;
     const uint32_t nb2 = 1u << d2;
-    if (p32) return tilepass_blocks(k_tilepass<LayP32, LayP32>, tilepass_lds<LayP32>(nb2));
+    if (lay == Layout::P32)
+        return tilepass_blocks(k_tilepass<LayP32, LayP32>, tilepass_lds<LayP32>(nb2));
     // as bucket_sort: 16-byte tuples write LayP40 where the plan allows it
     RangePlan P{};
     P.D2 = d2;
@@ -2782,22 +2783,24 @@ bool bucket_sort(Workspace* ws, const BucketSortArgs& a, hipStream_t st) {
     set_lds_attr((const void*)k_preft, PT_TILES * ((1 << kMaxD2) + 1) * 2);
     set_pass_attrs<LayTup>();
     if (a.host_plan && a.seg_start[0] && a.part_flag) {
-        if (a.p32) return bucket_sort_nosync<LayP32>(ws, a, st);
-        // 16-byte tuples only: with 8-byte tuples the group pass gained
-        // less than the byte plane cost it (the join 2.542-2.551 ms either
-        // way, the group pass 0.911-0.921 -> 0.930 ms, its SQ wait share
-        // 0.49 -> 0.56; profiles/r05_lab/p40_ab.txt, r05_sq_join8*)
-        if (a.p48)
-            return SMJ_P40 && sizeof(Tup) == 16 && LayP40::holds(*a.host_plan)
-                ? bucket_sort_nosync<LayP48, LayP40>(ws, a, st)
-                : bucket_sort_nosync<LayP48>(ws, a, st);
+        switch (a.layout) {
+            case Layout::P32: return bucket_sort_nosync<LayP32>(ws, a, st);
+            // 16-byte tuples only: with 8-byte tuples the group pass gained
+            // less than the byte plane cost it (the join 2.542-2.551 ms either
+            // way, the group pass 0.911-0.921 -> 0.930 ms, its SQ wait share
+            // 0.49 -> 0.56; profiles/r05_lab/p40_ab.txt, r05_sq_join8*)
+            case Layout::P48:
+                return SMJ_P40 && sizeof(Tup) == 16 && LayP40::holds(*a.host_plan)
+                    ? bucket_sort_nosync<LayP48, LayP40>(ws, a, st)
+                    : bucket_sort_nosync<LayP48>(ws, a, st);
 #ifdef KEY_8B
-        if (a.packed) return bucket_sort_nosync<LayPacked>(ws, a, st);
-        if (a.p96) return bucket_sort_nosync<LayP96>(ws, a, st);
+            case Layout::Words: return bucket_sort_nosync<LayPacked>(ws, a, st);
+            case Layout::P96: return bucket_sort_nosync<LayP96>(ws, a, st);
 #endif
-        return bucket_sort_nosync<LayTup>(ws, a, st);
+            default: return bucket_sort_nosync<LayTup>(ws, a, st);
+        }
     }
-    if (a.packed || a.stage != 7) {
+    if (a.layout != Layout::Tuples || a.stage != 7) {
         fprintf(stderr, "[ERROR] smj: packed or staged bucket sorts need the host plan\n");
         abort();
     }

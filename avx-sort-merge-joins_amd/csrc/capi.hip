@@ -169,10 +169,6 @@ static void choose_levels(uint64_t n, uint32_t want_d1, uint32_t* D1,
     *D2cap = d2 + 2 < kMaxD2 ? d2 + 2 : (d2 > kMaxD2 ? d2 : kMaxD2);
 }
 
-// level-1 partition of sorts and joins: sampled regions (no histogram pass)
-// unless the workspace's layout policy turns them off (smj_workspace_set_layouts)
-static bool use_sampled(const Workspace* ws) { return !(ws->layouts_off & SMJ_LAYOUT_NO_SAMPLED); }
-
 // exact key range [min, max] of the relations (one read pass); min > max
 // when they are empty.  16-byte non-temporal loads over one contiguous chunk
 // per workgroup, two register tiles of KR_U alternating (the scalar 8-byte
@@ -294,20 +290,36 @@ bool key_range(Workspace* ws, const Tup* const* rels, const uint64_t* ns, int nr
 }
 }  // namespace smj
 
-// 16-byte sorts and joins carry packed words through the intermediate passes
-// when the plan allows it (LayPacked) ...
-static bool use_packing(const Workspace* ws) { return !(ws->layouts_off & SMJ_LAYOUT_NO_PACKED); }
-
-// ... and 48-bit words in two planes first (LayP48) when every payload fits
-// 48 - s1 bits
-static bool use_p48(const Workspace* ws) { return !(ws->layouts_off & SMJ_LAYOUT_NO_P48); }
-
-// ... and 32-bit words before those (LayP32) where the payloads are tiny
-static bool use_p32(const Workspace* ws) { return !(ws->layouts_off & SMJ_LAYOUT_NO_P32); }
-
-// ... and, where no packed word holds the payloads, 12-byte elements (LayP96:
-// the payload and a 32-bit key offset) instead of the 16-byte tuples
-static bool use_p96(const Workspace* ws) { return !(ws->layouts_off & SMJ_LAYOUT_NO_P96); }
+// What the plan and the workspace's layout policy (smj_workspace_set_layouts)
+// allow the ladder of layout_policy.hpp.  Packed words of any width need the
+// sampled partition and the plan on the host.  16-byte tuples carry 64-bit
+// words (LayPacked), and 48-bit words in two planes (LayP48) under the same
+// conditions; 8-byte tuples have the 48-bit ones only.  The 48-bit scatter's
+// carries (128 bytes a partition) fit LDS up to 512 partitions.  Where no
+// packed word holds the payloads, 16-byte tuples travel as 12-byte elements
+// (LayP96: the payload and a 32-bit key offset) where the plan spans at most
+// 2^32 keys; with 16-element segments their carries fit 512 partitions too.
+static LayoutCaps layout_caps(const Workspace* ws, const RangePlan& hplan, uint32_t nb,
+                              bool sampled, bool plan_on_host, bool p48_fits) {
+    const uint32_t off = ws->layouts_off;
+    const bool words = sampled && plan_on_host && !(off & SMJ_LAYOUT_NO_PACKED);
+    LayoutCaps c;
+    c.sampled = sampled;
+    c.plan_on_host = plan_on_host;
+    c.p48_fits = p48_fits;
+    c.p32_usable = words && !(off & SMJ_LAYOUT_NO_P32) && LayP32::usable(hplan);
+#ifdef KEY_8B
+    c.can_pack = words && LayPacked::usable(hplan);
+    c.p48_ok = c.can_pack && !(off & SMJ_LAYOUT_NO_P48) && nb <= 512;
+    c.p96_ok = sampled && plan_on_host && !(off & SMJ_LAYOUT_NO_P96) && LayP96::usable(hplan) &&
+               nb <= (LayP96::Pack::kStoreBytes < 8 ? 512u : 1024u);
+#else
+    c.can_pack = false;
+    c.p48_ok = words && !(off & SMJ_LAYOUT_NO_P48) && LayP48::usable(hplan) && nb <= 512;
+    c.p96_ok = false;
+#endif
+    return c;
+}
 
 // Sort of one relation (nrel 1) or sort + merge-join count of two (nrel 2):
 // range plan -> sampled level-1 partition -> tile pass -> group pass.  The
@@ -334,7 +346,9 @@ static void device_bucket(Workspace* ws, const Tup* const* rels, const uint64_t*
     choose_levels(nmax, fanout_bits, &D1, &D2, &D2cap);
     RangePlan* plan = (RangePlan*)ws->scratch("plan", sizeof(RangePlan));
     uint32_t nb = 1u << D1;
-    const bool sampled = use_sampled(ws) && D1 <= 10;  // LDS carries up to 1024
+    // level 1: sampled regions (no histogram pass) unless the workspace's
+    // layout policy turns them off; the scatter's LDS carries hold up to 1024
+    const bool sampled = !(ws->layouts_off & SMJ_LAYOUT_NO_SAMPLED) && D1 <= 10;
     bool plan_on_host = hint_min <= hint_max;
     // a guessed plan is verified by the sampled scatter only
     bool guessed = false;
@@ -349,11 +363,6 @@ static void device_bucket(Workspace* ws, const Tup* const* rels, const uint64_t*
     RangePlan hplan = make_plan(hint_min, hint_max, D1, D2, D2cap, kGroupD3Max);
     if (!plan_on_host)
         plan_from_sample(ws, rels, ns, nrel, D1, D2, D2cap, hint_min, hint_max, plan, st);
-#ifdef KEY_8B
-    bool can_pack = sampled && plan_on_host && use_packing(ws) && LayPacked::usable(hplan);
-#else
-    const bool can_pack = false;
-#endif
     Tup* part[2] = {nullptr, nullptr};
     uint64_t* bst[2] = {nullptr, nullptr};
     int64_t* bh[2] = {nullptr, nullptr};
@@ -398,117 +407,59 @@ static void device_bucket(Workspace* ws, const Tup* const* rels, const uint64_t*
     };
     unsigned long long* cnt = count_dev
         ? count_dev : (unsigned long long*)ws->scratch("sort_cnt", 8);
-    // attempts: sampled + 48-bit words (-1), sampled + packed words (0),
-    // sampled tuples (1), exact tuples (2); a later one runs only when the one
-    // before reported a region overflow or an unpackable tuple (its tile and
-    // group passes then did nothing or are discarded: the count restarts from
-    // 0).  A payload too wide for 48 bits but not for 64 goes from -1 to 0.  A
-    // guessed plan that a key falls outside of is replaced by the exact one
-    // and the attempts restart.  The 48-bit scatter's carries (128 bytes a
-    // partition) fit LDS up to 512 partitions.
-    // (8-byte tuples have no 64-bit packed words: the 48-bit ones, else
-    // tuples; the same conditions as packing, checked here)
     // A 48-bit word keeps 48 - s1 payload bits.  Payloads are taken to lie
     // within the key span (the row ids of a PK relation, as in the
     // benchmark): where they would not, the 48-bit attempt would fail on them
     // and partition a second time, so the join starts with 64-bit words (the
-    // 1024M x 1024M join: 2^9 partitions leave 27 payload bits).
+    // 1024M x 1024M join: 2^9 partitions leave 27 payload bits).  From the
+    // first plan of the call: kept when a guessed plan is replaced.
     const bool p48_fits = hplan.s1 >= 1 && hplan.s1 <= 32 && hplan.span < (1ull << (48 - hplan.s1));
     const uint64_t shape = ((uint64_t)nrel << 62) ^ ns[0] ^ (nrel > 1 ? ns[1] << 31 : 0);
-    Workspace::ShapeHint& H = ws->hint_for(shape);
-    // 48-bit words, whatever their payloads
-    auto p48_ok = [&]() {
-#ifdef KEY_8B
-        return can_pack && use_p48(ws) && nb <= 512;
-#else
-        return sampled && plan_on_host && use_packing(ws) && use_p48(ws) &&
-               LayP48::usable(hplan) && nb <= 512;
-#endif
-    };
-    // 32-bit words (mode -2) are tried first: nothing tells the payloads'
-    // width beforehand, and a shape whose payloads did not fit does not try
-    // them again (Workspace::ShapeHint::p32_fail)
-    auto first_mode = [&]() {
-        if (sampled && plan_on_host && use_packing(ws) && use_p32(ws) &&
-            LayP32::usable(hplan) && !H.p32_fail)
-            return -2;
-        if (p48_ok() && p48_fits) return -1;
-        return can_pack ? 0 : (sampled ? 1 : 2);
-    };
-    // The layout hint of the workspace: when the last call of the same shape
-    // had to leave the narrower layouts because of its payloads (too wide for
-    // 48-bit words, or for packed words at all), start at the layout it
-    // reached -- its partition would only be repeated -- and re-probe from the
-    // top every 16th call.  Data-dependent like the fallback it skips; the
-    // results are the same in every layout.
-    bool hinted = false;
-    auto hinted_mode = [&](int m) {
-        hinted = false;
-        if (H.mode_hint <= m || ++H.calls % 16 == 0) return m;
-        const int h = H.mode_hint == 0 ? (can_pack ? 0 : (sampled ? 1 : 2))
-                                         : (sampled ? 1 : 2);
-        hinted = h > m;
-        return h > m ? h : m;
-    };
-    // the sampled tuples' attempt (mode 1) on 16-byte tuples: 12-byte
-    // elements where the plan spans at most 2^32 keys (LayP96)
-    auto p96_ok = [&]() {
-#ifdef KEY_8B
-        // (16-element segments: the scatter's carries fit LDS up to 512
-        // partitions, as for the 48-bit words)
-        return sampled && plan_on_host && use_p96(ws) && LayP96::usable(hplan) &&
-               nb <= (LayP96::Pack::kStoreBytes < 8 ? 512u : 1024u);
-#else
-        return false;
-#endif
-    };
-    int mode = hinted_mode(first_mode());
-    const bool started_hinted = hinted;
-    int payload_fb = -2;  // the mode a payload flag sent this call to
-    while (mode <= 2) {
-        if (mode >= 1) tuple_plan();
-        const bool p32 = mode == -2;
-        const bool p48 = mode == -1;
-        const bool packed = mode <= 0;
-        const bool p96 = mode == 1 && p96_ok();
-        // the status word the tile and group passes exit on (sampled modes)
-        const bool check = packed || p96 || (guessed && mode == 1);
+    ShapeHint& H = ws->hint_for(shape);
+    // (the caps follow the plan and the partition count, which change)
+    auto caps_now = [&]() { return layout_caps(ws, hplan, nb, sampled, plan_on_host, p48_fits); };
+    // the ladder of layout_policy.hpp: a later attempt runs only when the one
+    // before was void (its passes did nothing or are discarded: the count
+    // restarts from 0)
+    bool started_hinted = false, rehinted = false;
+    Rung rung = first_rung(caps_now(), H, &started_hinted);
+    Rung payload_fb = Rung::P32;  // none
+    Layout lay = Layout::Tuples;
+    for (;;) {
+        if (rung >= Rung::Sampled) tuple_plan();
+        const LayoutCaps caps = caps_now();
+        lay = layout_of(rung, caps.p96_ok);
+        const bool exact = rung == Rung::Exact;
+        const bool planes = lay == Layout::P48 || lay == Layout::P96;
+        // the status word the tile and group passes exit on (sampled rungs)
+        const bool check = lay != Layout::Tuples || (guessed && rung == Rung::Sampled);
+        unsigned int* bad = check ? status + 1 : nullptr;
         hipLaunchKernelGGL(k_join_begin, dim3(1), dim3(256), 0, st, plan, hplan,
                            plan_on_host ? 1 : 0, cnt, status, sample,
-                           mode < 2 ? (uint32_t)nrel * nb : 0u);
-        // LayP48's plane stride: the partition buffer's capacity in elements,
+                           exact ? 0u : (uint32_t)nrel * nb);
+        // the planes' stride: the partition buffer's capacity in elements,
         // rounded to 32 (the hi plane starts 16-byte aligned); the buffer
-        // holds 16 bytes an element, the planes take 6
+        // holds 16 bytes an element, the planes take 6 or 12
         uint64_t pstride[2] = {0, 0};
-        for (int r = 0; r < nrel && (p48 || p96); r++)
+        for (int r = 0; r < nrel && planes; r++)
             pstride[r] = (sampled_capacity(ns[r], D1) + 31) & ~31ull;
-        if (mode < 2) {
-            void* outs_v[2] = {part[0], part[nrel > 1 ? 1 : 0]};
-            if ((p48 || p96) && nrel > 1 && pstride[0] != pstride[1]) {
-                // one stride per launch: the two relations take turns.  Both
-                // calls use relation 0's region scratch (cursor, cap_end):
-                // correct because they run in order on the one stream `st`
-                for (int r = 0; r < nrel; r++) {
-                    const Tup* rr1[1] = {rels[r]};
-                    const uint64_t nn1[1] = {ns[r]};
-                    void* oo1[1] = {part[r]};
-                    uint64_t* bs1[1] = {bst[r]};
-                    int64_t* bh1[1] = {bh[r]};
-                    uint64_t* sgs1[1] = {sgs[r]};
-                    int64_t* sgc1[1] = {sgc[r]};
-                    sampled_partition(ws, 1, rr1, nn1, oo1, plan, D1, sample + (size_t)r * nb,
-                                      bs1, bh1, sgs1, sgc1, status, st, &hplan, true,
-                                      status + 1, pstride[r], false, false, p96);
-                }
-            } else {
-                sampled_partition(ws, nrel, rels, ns, outs_v, plan, D1, sample, bst, bh, sgs,
-                                  sgc, status, st, plan_on_host ? &hplan : nullptr,
-                                  packed || p96, check ? status + 1 : nullptr, pstride[0], p32,
-                                  false, p96);
-            }
-        } else {
+        if (exact) {
             for (int r = 0; r < nrel; r++)
                 plan_partition(ws, rels[r], ns[r], part[r], plan, D1, bst[r], bh[r], st);
+        } else if (planes && nrel > 1 && pstride[0] != pstride[1]) {
+            // one stride per launch: the two relations take turns.  Both
+            // calls use relation 0's region scratch (cursor, cap_end):
+            // correct because they run in order on the one stream `st`
+            for (int r = 0; r < nrel; r++) {
+                void* out1 = part[r];
+                sampled_partition(ws, 1, rels + r, ns + r, &out1, plan, D1,
+                                  sample + (size_t)r * nb, bst + r, bh + r, sgs + r, sgc + r,
+                                  status, st, lay, &hplan, bad, pstride[r]);
+            }
+        } else {
+            void* outs_v[2] = {part[0], part[nrel > 1 ? 1 : 0]};
+            sampled_partition(ws, nrel, rels, ns, outs_v, plan, D1, sample, bst, bh, sgs, sgc,
+                              status, st, lay, plan_on_host ? &hplan : nullptr, bad, pstride[0]);
         }
         SMJ_CHECK(hipEventRecord(ws->ev[1], st));
         BucketSortArgs a;
@@ -519,10 +470,11 @@ static void device_bucket(Workspace* ws, const Tup* const* rels, const uint64_t*
             a.tmp[r] = part[r];
             a.out[r] = r < nrel ? outs[r] : nullptr;
             a.n[r] = r < nrel ? ns[r] : 0;
-            if (mode < 2) {
+            if (!exact) {
                 a.seg_start[r] = sgs[r];
                 a.seg_cnt[r] = sgc[r];
             }
+            a.pstride[r] = pstride[r];
         }
         a.nrel = nrel;
         a.nbuckets = nb;
@@ -532,43 +484,17 @@ static void device_bucket(Workspace* ws, const Tup* const* rels, const uint64_t*
         a.ev_bucket = ws->ev[2];
         a.ev_ovf = ws->ev[3];
         a.host_plan = plan_on_host ? &hplan : nullptr;
-        a.packed = packed;
-        a.p48 = p48;
-        a.p32 = p32;
-        a.p96 = p96;
-        a.pstride[0] = pstride[0];
-        a.pstride[1] = pstride[1];
-        a.pack_bad = check ? status + 1 : nullptr;
+        a.layout = lay;
+        a.pack_bad = bad;
         a.status = status;
-        if (mode < 2) a.part_flag = status;
+        if (!exact) a.part_flag = status;
         uint32_t why[2] = {0, 0};
         a.status_out = why;
         if (bucket_sort(ws, a, st)) break;
-        if (mode == -2 && !(guessed && (why[1] & kBadRange))) {
-            // payloads too wide for 32 bits: the narrowest wider words that
-            // hold them; anything else (overflow, a key outside the plan) as
-            // from 64-bit words
-            const bool pay = !why[0] && !(why[1] & kBadRange);
-            if (pay && (why[1] & (kBadPayload | kBadPayload48 | kBadPayload32)))
-                H.p32_fail = true;
-            if (pay && !(why[1] & (kBadPayload | kBadPayload48)) && p48_ok())
-                mode = -1;
-            else if (pay && !(why[1] & kBadPayload) && can_pack)
-                mode = 0;
-            else
-                mode = 1;
-            continue;
-        }
-        if (mode == -1 && !(guessed && (why[1] & kBadRange))) {
-            // payloads too wide for 48 bits only: 64-bit words; anything else
-            // (overflow, unpackable) as from 64-bit words
-            mode = (why[1] & kBadPayload48) && !(why[1] & kBadPayload) && !why[0] && can_pack
-                ? 0 : 1;
-            if (!why[0] && (why[1] & (kBadPayload | kBadPayload48)) && !(why[1] & kBadRange))
-                payload_fb = mode;
-            continue;
-        }
-        if (guessed && (why[1] & kBadRange)) {
+        const Next next = after_void(rung, caps, why, guessed, H, &payload_fb);
+        if (next.what == Next::Stop) break;
+        rung = next.rung;
+        if (next.what == Next::Restart) {
             // a key outside 1..size_guess: the exact plan, attempts from the top
             guessed = false;
             plan_on_host = key_range(ws, rels, ns, nrel, &hint_min, &hint_max, st);
@@ -576,23 +502,16 @@ static void device_bucket(Workspace* ws, const Tup* const* rels, const uint64_t*
             if (!plan_on_host)  // empty relations never report a bad key
                 plan_from_sample(ws, rels, ns, nrel, D1, D2, D2cap, hint_min, hint_max, plan,
                                  st);
-#ifdef KEY_8B
-            can_pack = sampled && plan_on_host && use_packing(ws) && LayPacked::usable(hplan);
-#endif
-            mode = hinted_mode(first_mode());
-            continue;
+            rung = first_rung(caps_now(), H, &rehinted);
         }
-        if (mode == 0 && !why[0] && (why[1] & kBadPayload) && !(why[1] & kBadRange))
-            payload_fb = 1;
-        mode++;
     }
-    ws->last_layout = mode == -2 ? SMJ_LAYOUT_USED_P32 : mode == -1 ? SMJ_LAYOUT_USED_P48
-                    : mode == 0 ? SMJ_LAYOUT_USED_WORDS
-                    : mode == 1 && p96_ok() ? SMJ_LAYOUT_USED_P96 : SMJ_LAYOUT_USED_TUPLES;
-    if (payload_fb >= 0)
-        H.mode_hint = payload_fb;
-    else if (!started_hinted)
-        H.mode_hint = -2;  // the narrow layouts held (or failed for other reasons)
+    static_assert((int)Layout::Tuples == SMJ_LAYOUT_USED_TUPLES &&
+                  (int)Layout::Words == SMJ_LAYOUT_USED_WORDS &&
+                  (int)Layout::P48 == SMJ_LAYOUT_USED_P48 &&
+                  (int)Layout::P32 == SMJ_LAYOUT_USED_P32 &&
+                  (int)Layout::P96 == SMJ_LAYOUT_USED_P96, "smj.h / layout_policy.hpp");
+    ws->last_layout = (int)lay;
+    end_hint(H, payload_fb, started_hinted);
     SMJ_CHECK(hipEventRecord(ws->ev[4], st));
 }
 
@@ -1784,8 +1703,7 @@ int smj_workspace_skew_stats(smj_workspace* ws, smj_skew_stats* out) {
 }
 
 int smj_tilepass_occupancy(int layout, uint32_t d2_bits) {
-    if (layout != SMJ_LAYOUT_USED_P48 && layout != SMJ_LAYOUT_USED_P32) return -1;
-    return tilepass_occupancy(layout == SMJ_LAYOUT_USED_P32, d2_bits);
+    return tilepass_occupancy((Layout)layout, d2_bits);
 }
 
 void smj_dev_partition(smj_workspace* ws, const tuple_t* in, uint64_t n,
@@ -1993,21 +1911,22 @@ static void join_segmented_core(Workspace* ws, void* R, uint64_t nR, void* S, ui
     if (D2 > kMaxD2) D2 = kMaxD2;
     D2cap = D2 + 2 < kMaxD2 ? D2 + 2 : (D2 > kMaxD2 ? D2 : kMaxD2);
     RangePlan hplan = make_plan(key_lo, key_hi, D1, D2, D2cap, kGroupD3Max);
-    const bool p48 = pstride != nullptr;  // 48-bit words in two planes (LayP48)
-    const bool packed = (flags & SMJ_SEG_PACKED) != 0 || p48;
-    if (p48 && !LayP48::usable(hplan)) {
+    // with strides: 48-bit words in two planes (LayP48)
+    const Layout lay = pstride ? Layout::P48
+                               : (flags & SMJ_SEG_PACKED) ? Layout::Words : Layout::Tuples;
+    if (lay == Layout::P48 && !LayP48::usable(hplan)) {
         fprintf(stderr, "[ERROR] smj_dev_join_segmented_planes: 48-bit words need "
                 "1 <= s1 <= 32 (s1 = %u)\n", hplan.s1);
         abort();
     }
 #ifdef KEY_8B
-    if (packed && !p48 && !LayPacked::usable(hplan)) {
+    if (lay == Layout::Words && !LayPacked::usable(hplan)) {
         fprintf(stderr, "[ERROR] smj_dev_join_segmented: packed words need 1 <= s1 <= 32 "
                 "(s1 = %u)\n", hplan.s1);
         abort();
     }
 #else
-    if (packed && !p48) {
+    if (lay == Layout::Words) {
         fprintf(stderr, "[ERROR] smj_dev_join_segmented: packed words are a 16-byte-tuple "
                 "layout\n");
         abort();
@@ -2048,10 +1967,9 @@ static void join_segmented_core(Workspace* ws, void* R, uint64_t nR, void* S, ui
     SMJ_CHECK(hipMemsetAsync(flag, 0, 4, st));
     a.part_flag = flag;  // never set: the buckets are exact
     a.host_plan = &hplan;
-    a.packed = packed;  // checked packable before the exchange: no pack_bad here
-    a.digit_fast = packed;  // packed words never lie outside the plan
-    a.p48 = p48;
-    for (int r = 0; r < 2 && p48; r++) a.pstride[r] = pstride[r];
+    a.layout = lay;  // words: checked packable before the exchange, no pack_bad here
+    a.digit_fast = lay != Layout::Tuples;  // packed words never lie outside the plan
+    for (int r = 0; r < 2 && pstride; r++) a.pstride[r] = pstride[r];
     if ((flags & SMJ_SEG_STAGE_R) && (flags & SMJ_SEG_STAGE_REST)) {
         fprintf(stderr, "[ERROR] smj_dev_join_segmented: SMJ_SEG_STAGE_R and _REST are two "
                 "calls\n");
@@ -2260,72 +2178,66 @@ void smj_dev_xrecv(const int64_t* msg, const int64_t* chunk, uint32_t world, uin
           (hipStream_t)stream);
 }
 
+// The sampled range partition of one relation, as the exchange of the
+// multi-GPU join uses it: uploads plan `h`, zeroes flags[0..1] and the
+// counters (`cname`: 2^nbits of them, kShards times as many when exact) and
+// partitions `in` into `lay`.
+static void range_partition(smj_workspace* wsp, const tuple_t* in, uint64_t n, void* out,
+                            uint32_t nbits, const RangePlan& h, Layout lay, uint64_t stride,
+                            bool exact, const char* cname, int64_t* seg_start_out,
+                            int64_t* seg_cnt_out, unsigned int* flags, smj_stream_t stream) {
+    Workspace* ws = (Workspace*)wsp;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nbins = 1u << nbits;
+    RangePlan* plan = (RangePlan*)ws->scratch("xp_plan", sizeof(RangePlan));
+    hipLaunchKernelGGL(k_setplan, dim3(1), dim3(1), 0, st, plan, h);
+    const size_t cbytes = (size_t)nbins * (exact ? kShards : 1) * 4;
+    unsigned int* counts = (unsigned int*)ws->scratch(cname, cbytes);
+    SMJ_CHECK(hipMemsetAsync(counts, 0, cbytes, st));
+    SMJ_CHECK(hipMemsetAsync(flags, 0, 8, st));
+    uint64_t* starts = (uint64_t*)ws->scratch("xp_starts", (size_t)nbins * 8);
+    int64_t* hist = (int64_t*)ws->scratch("xp_hist", (size_t)nbins * 8);
+    const Tup* rel = (const Tup*)in;
+    uint64_t* ss = (uint64_t*)seg_start_out;
+    sampled_partition(ws, 1, &rel, &n, &out, plan, nbits, counts, &starts, &hist, &ss,
+                      &seg_cnt_out, flags, st, lay, &h, lay != Layout::Tuples ? flags + 1 : nullptr,
+                      stride, exact);
+}
+
+// the plan of a range partition into tuples or (packed) 64-bit words; false
+// where the sampled scatter or the words do not apply
+static bool range_plan(uint32_t nbits, uint64_t n, int64_t key_min, int64_t key_max, int packed,
+                       RangePlan* h) {
+    if (nbits > 10 || n >= (1ull << 32)) return false;  // LDS carries: up to 1024 partitions
+    *h = make_plan(key_min, key_max, nbits, 0, 0, 0);
+#ifdef KEY_8B
+    return !packed || LayPacked::usable(*h);
+#else
+    return !packed;
+#endif
+}
+
 int smj_dev_partition_range_sampled(smj_workspace* wsp, const tuple_t* in, uint64_t n,
                                     void* out, uint32_t nbits, int64_t key_min,
                                     int64_t key_max, int packed, int64_t* seg_start_out,
                                     int64_t* seg_cnt_out, unsigned int* flags,
                                     smj_stream_t stream) {
-    Workspace* ws = (Workspace*)wsp;
-    hipStream_t st = (hipStream_t)stream;
-    if (nbits > 10 || n >= (1ull << 32)) return 0;  // LDS carries: up to 1024 partitions
-    RangePlan h = make_plan(key_min, key_max, nbits, 0, 0, 0);
-#ifdef KEY_8B
-    if (packed && !LayPacked::usable(h)) return 0;
-#else
-    if (packed) return 0;
-#endif
-    const uint32_t nbins = 1u << nbits;
-    RangePlan* plan = (RangePlan*)ws->scratch("xp_plan", sizeof(RangePlan));
-    hipLaunchKernelGGL(k_setplan, dim3(1), dim3(1), 0, st, plan, h);
-    unsigned int* sample = (unsigned int*)ws->scratch("xp_sample", (size_t)nbins * 4);
-    SMJ_CHECK(hipMemsetAsync(sample, 0, (size_t)nbins * 4, st));
-    SMJ_CHECK(hipMemsetAsync(flags, 0, 8, st));
-    uint64_t* starts = (uint64_t*)ws->scratch("xp_starts", (size_t)nbins * 8);
-    int64_t* hist = (int64_t*)ws->scratch("xp_hist", (size_t)nbins * 8);
-    const Tup* rels[1] = {(const Tup*)in};
-    const uint64_t ns[1] = {n};
-    void* outs[1] = {out};
-    uint64_t* st_[1] = {starts};
-    int64_t* h_[1] = {hist};
-    uint64_t* ss[1] = {(uint64_t*)seg_start_out};
-    int64_t* sc[1] = {seg_cnt_out};
-    sampled_partition(ws, 1, rels, ns, outs, plan, nbits, sample, st_, h_, ss, sc, flags, st,
-                      &h, packed != 0, packed ? flags + 1 : nullptr);
+    RangePlan h;
+    if (!range_plan(nbits, n, key_min, key_max, packed, &h)) return 0;
+    range_partition(wsp, in, n, out, nbits, h, packed ? Layout::Words : Layout::Tuples, 0, false,
+                    "xp_sample", seg_start_out, seg_cnt_out, flags, stream);
     return 1;
 }
 
+// exact (partition, shard) counts instead of a sample
 int smj_dev_partition_range_shards(smj_workspace* wsp, const tuple_t* in, uint64_t n,
                                    void* out, uint32_t nbits, int64_t key_min, int64_t key_max,
                                    int packed, int64_t* seg_start_out, int64_t* seg_cnt_out,
                                    unsigned int* flags, smj_stream_t stream) {
-    Workspace* ws = (Workspace*)wsp;
-    hipStream_t st = (hipStream_t)stream;
-    if (nbits > 10 || n >= (1ull << 32)) return 0;  // the scatter's LDS carries
-    RangePlan h = make_plan(key_min, key_max, nbits, 0, 0, 0);
-#ifdef KEY_8B
-    if (packed && !LayPacked::usable(h)) return 0;
-#else
-    if (packed) return 0;
-#endif
-    const uint32_t nbins = 1u << nbits;
-    RangePlan* plan = (RangePlan*)ws->scratch("xp_plan", sizeof(RangePlan));
-    hipLaunchKernelGGL(k_setplan, dim3(1), dim3(1), 0, st, plan, h);
-    // exact (partition, shard) counts instead of a sample
-    unsigned int* counts =
-        (unsigned int*)ws->scratch("xp_shard_counts", (size_t)nbins * kShards * 4);
-    SMJ_CHECK(hipMemsetAsync(counts, 0, (size_t)nbins * kShards * 4, st));
-    SMJ_CHECK(hipMemsetAsync(flags, 0, 8, st));
-    uint64_t* starts = (uint64_t*)ws->scratch("xp_starts", (size_t)nbins * 8);
-    int64_t* hist = (int64_t*)ws->scratch("xp_hist", (size_t)nbins * 8);
-    const Tup* rels[1] = {(const Tup*)in};
-    const uint64_t ns[1] = {n};
-    void* outs[1] = {out};
-    uint64_t* st_[1] = {starts};
-    int64_t* h_[1] = {hist};
-    uint64_t* ss[1] = {(uint64_t*)seg_start_out};
-    int64_t* sc[1] = {seg_cnt_out};
-    sampled_partition(ws, 1, rels, ns, outs, plan, nbits, counts, st_, h_, ss, sc, flags, st,
-                      &h, packed != 0, packed ? flags + 1 : nullptr, 0, false, true);
+    RangePlan h;
+    if (!range_plan(nbits, n, key_min, key_max, packed, &h)) return 0;
+    range_partition(wsp, in, n, out, nbits, h, packed ? Layout::Words : Layout::Tuples, 0, true,
+                    "xp_shard_counts", seg_start_out, seg_cnt_out, flags, stream);
     return 1;
 }
 
@@ -2334,8 +2246,6 @@ int smj_dev_partition_range_planes(smj_workspace* wsp, const tuple_t* in, uint64
                                    int64_t key_min, int64_t key_max, int64_t* seg_start_out,
                                    int64_t* seg_cnt_out, unsigned int* flags,
                                    smj_stream_t stream) {
-    Workspace* ws = (Workspace*)wsp;
-    hipStream_t st = (hipStream_t)stream;
     // the scatter's LDS carries hold 2^10 partitions of 48-bit words with its
     // 16-byte segments (round 6; 2^9 was the limit of 64-byte segments)
     if (nbits > 10 || n >= (1ull << 32)) return 0;
@@ -2347,23 +2257,8 @@ int smj_dev_partition_range_planes(smj_workspace* wsp, const tuple_t* in, uint64
                 (unsigned long long)sampled_capacity(n, nbits));
         abort();
     }
-    const uint32_t nbins = 1u << nbits;
-    RangePlan* plan = (RangePlan*)ws->scratch("xp_plan", sizeof(RangePlan));
-    hipLaunchKernelGGL(k_setplan, dim3(1), dim3(1), 0, st, plan, h);
-    unsigned int* sample = (unsigned int*)ws->scratch("xp_sample", (size_t)nbins * 4);
-    SMJ_CHECK(hipMemsetAsync(sample, 0, (size_t)nbins * 4, st));
-    SMJ_CHECK(hipMemsetAsync(flags, 0, 8, st));
-    uint64_t* starts = (uint64_t*)ws->scratch("xp_starts", (size_t)nbins * 8);
-    int64_t* hist = (int64_t*)ws->scratch("xp_hist", (size_t)nbins * 8);
-    const Tup* rels[1] = {(const Tup*)in};
-    const uint64_t ns[1] = {n};
-    void* outs[1] = {out};
-    uint64_t* st_[1] = {starts};
-    int64_t* h_[1] = {hist};
-    uint64_t* ss[1] = {(uint64_t*)seg_start_out};
-    int64_t* sc[1] = {seg_cnt_out};
-    sampled_partition(ws, 1, rels, ns, outs, plan, nbits, sample, st_, h_, ss, sc, flags, st,
-                      &h, true, flags + 1, stride);
+    range_partition(wsp, in, n, out, nbits, h, Layout::P48, stride, false, "xp_sample",
+                    seg_start_out, seg_cnt_out, flags, stream);
     return 1;
 }
 

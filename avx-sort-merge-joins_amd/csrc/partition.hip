@@ -2150,40 +2150,42 @@ static void sampled_scatter(Workspace* ws, const Tup* in, uint64_t n, void* out,
     abort();
 }
 
+// a layout's Pack for the host plan holds the key base, the span and, where
+// it has one, the level-1 shift (LayP96::Pack has none)
+template <class Pack>
+static auto set_s1(Pack& pk, const RangePlan& p, int) -> decltype((void)pk.s1) { pk.s1 = p.s1; }
+template <class Pack>
+static void set_s1(Pack&, const RangePlan&, long) {}
+
 void sampled_partition(Workspace* ws, int nrel, const Tup* const* in, const uint64_t* n,
                        void* const* out, const RangePlan* plan_dev, uint32_t dbits,
                        unsigned int* sample, uint64_t* const* starts_dev,
                        int64_t* const* hist_out, uint64_t* const* seg_start,
                        int64_t* const* seg_cnt, unsigned int* flag_dev, hipStream_t st,
-                       const RangePlan* host_plan, bool packed, unsigned int* bad,
-                       uint64_t p48_stride, bool p32, bool exact, bool p96) {
+                       Layout lay, const RangePlan* host_plan, unsigned int* bad,
+                       uint64_t pstride, bool exact) {
     PlanDigit1 dig{plan_dev};
     const uint32_t nbins = 1u << dbits;
-    // p96 (16-byte tuples): LayP96 elements in two planes of p48_stride
-    // elements (int64 payloads, then uint32 key offsets)
-    if (p96 && (sizeof(Tup) != 16 || !host_plan || !p48_stride || p32 || exact)) {
+    // LayP96: two planes of pstride elements (int64 payloads, uint32 key offsets)
+    if (lay == Layout::P96 && (sizeof(Tup) != 16 || !host_plan || !pstride)) {
         fprintf(stderr, "[ERROR] smj: the 96-bit layout needs 16-byte tuples, the host plan "
                         "and a plane stride\n");
         abort();
     }
-    if (exact && (p48_stride || p32)) {
+    if (exact && lay != Layout::Tuples && lay != Layout::Words) {
         fprintf(stderr, "[ERROR] smj: exact shard regions take tuples or 64-bit words\n");
         abort();
     }
-#ifndef KEY_8B
-    // 8-byte tuples: no 64-bit packed words, but 48- and 32-bit ones
-    packed = p48_stride != 0 || p32;
-#endif
-    if (p32 && (p48_stride || !packed)) {
-        fprintf(stderr, "[ERROR] smj: the 32-bit layout is a packed one-plane layout\n");
+    if (lay == Layout::Words && sizeof(Tup) != 16) {
+        fprintf(stderr, "[ERROR] smj: packed words are a 16-byte-tuple layout\n");
         abort();
     }
-    // p48_stride > 0: 48-bit words in two planes of that many elements (LayP48)
-    if (p48_stride && !packed) {
-        fprintf(stderr, "[ERROR] smj: the 48-bit layout is a packed layout\n");
+    // 48-bit words in two planes of pstride elements (LayP48)
+    if (lay == Layout::P48 && !pstride) {
+        fprintf(stderr, "[ERROR] smj: the 48-bit layout needs a plane stride\n");
         abort();
     }
-    if (packed && !host_plan) {
+    if (lay != Layout::Tuples && !host_plan) {
         fprintf(stderr, "[ERROR] smj: packed partition needs the host plan\n");
         abort();
     }
@@ -2217,13 +2219,10 @@ void sampled_partition(Workspace* ws, int nrel, const Tup* const* in, const uint
         TraceScope ts(ws, "k_hist", st);
         for (int r = 0; r < nrel; r++) {
             if (!n[r]) continue;
-            int items = 0;
+            int items = sampled_items<PackRange>(nbins);
 #ifdef KEY_8B
-            if (packed)
-                items = sampled_items<LayPacked::Pack>(nbins);
-            else
+            if (lay == Layout::Words) items = sampled_items<LayPacked::Pack>(nbins);
 #endif
-                items = sampled_items<PackRange>(nbins);
             if (!items) {
                 fprintf(stderr, "[ERROR] smj: sampled scatter LDS exceeds 160 KiB (%u "
                         "partitions)\n", nbins);
@@ -2255,50 +2254,29 @@ void sampled_partition(Workspace* ws, int nrel, const Tup* const* in, const uint
         // elements, so the hi plane's regions start on 64 bytes)
         hipLaunchKernelGGL(k_regions, dim3(nrel), dim3(256), 0, st, R, nbins, kSampleStride,
                            kRegionSlack,
-                           p96 ? (uint32_t)SMJ_P96_SEGB : p48_stride || p32 ? 4u : packed ? 8u
-                                                                     : (uint32_t)sizeof(Tup));
+                           lay == Layout::P96 ? (uint32_t)SMJ_P96_SEGB
+                           : lay == Layout::P48 || lay == Layout::P32 ? 4u
+                           : lay == Layout::Words ? 8u : (uint32_t)sizeof(Tup));
     }
     for (int r = 0; r < nrel; r++) {
         if (!n[r]) continue;
-        if (p32) {
-            LayP32::Pack pk;
-            pk.bu = key_u(host_plan->base);
-            pk.span = host_plan->span;
-            pk.s1 = host_plan->s1;
-            sampled_scatter(ws, in[r], n[r], out[r], 0, dig, nbins, R.cursor[r], R.cap_end[r],
-                            pk, bad, st);
-            continue;
-        }
+        if (lay != Layout::Tuples) {
+            // (ostride: the planes' stride)
+            const auto go = [&](auto pk, uint64_t ostride) {
+                pk.bu = key_u(host_plan->base);
+                pk.span = host_plan->span;
+                set_s1(pk, *host_plan, 0);
+                sampled_scatter(ws, in[r], n[r], out[r], ostride, dig, nbins, R.cursor[r],
+                                R.cap_end[r], pk, bad, st);
+            };
+            if (lay == Layout::P32) go(LayP32::Pack(), 0);
+            else if (lay == Layout::P48) go(LayP48::Pack(), pstride);
 #ifdef KEY_8B
-        if (p96) {
-            LayP96::Pack pk;
-            pk.bu = key_u(host_plan->base);
-            pk.span = host_plan->span;
-            sampled_scatter(ws, in[r], n[r], out[r], p48_stride, dig, nbins, R.cursor[r],
-                            R.cap_end[r], pk, bad, st);
-            continue;
-        }
+            else if (lay == Layout::P96) go(LayP96::Pack(), pstride);
+            else go(LayPacked::Pack(), 0);
 #endif
-        if (p48_stride) {
-            LayP48::Pack pk;
-            pk.bu = key_u(host_plan->base);
-            pk.span = host_plan->span;
-            pk.s1 = host_plan->s1;
-            sampled_scatter(ws, in[r], n[r], out[r], p48_stride, dig, nbins, R.cursor[r],
-                            R.cap_end[r], pk, bad, st);
             continue;
         }
-#ifdef KEY_8B
-        if (packed) {
-            LayPacked::Pack pk;
-            pk.bu = key_u(host_plan->base);
-            pk.span = host_plan->span;
-            pk.s1 = host_plan->s1;
-            sampled_scatter(ws, in[r], n[r], out[r], 0, dig, nbins, R.cursor[r], R.cap_end[r],
-                            pk, bad, st);
-            continue;
-        }
-#endif
         // tuples: range-checked against the host plan when a flag is given
         PackRange pk{0ull, ~0ull};
         if (bad && host_plan) {

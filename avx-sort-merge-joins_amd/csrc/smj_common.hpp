@@ -30,6 +30,8 @@
 #include <set>
 #include <utility>
 
+#include "layout_policy.hpp"
+
 namespace smj {
 
 // hipFuncSetAttribute(kernel, MaxDynamicSharedMemorySize, bytes) once per
@@ -227,12 +229,7 @@ struct RefDigit {
 //   level-2 digit  d2 = (rel >> s2) - (d1 << D2)        (2^D2 per bucket)
 //   level-3 digit  d3 = (rel >> s3) - ((d1<<D2|d2) << D3)
 // ---------------------------------------------------------------------------
-// bits of a partition's "bad tuple" flag (status word 1 of a join)
-constexpr uint32_t kBadPayload = 1;  // a payload does not fit a packed word
-constexpr uint32_t kBadRange = 2;    // a key lies outside the plan range
-constexpr uint32_t kBadPayload48 = 4;  // ... fits a 64-bit word, not a 48-bit one
-constexpr uint32_t kBadPayload32 = 8;  // ... fits a 48-bit word, not a 32-bit one
-
+// (the bits of a partition's "bad tuple" flag, kBad*: layout_policy.hpp)
 struct RangePlan {
     int64_t base;     // smallest key of the range
     uint64_t span;    // 2^L - 1 (all-ones of width L), L <= 64

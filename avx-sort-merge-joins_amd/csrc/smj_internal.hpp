@@ -69,22 +69,9 @@ struct Workspace {
     // (smj_workspace_set_layouts, SMJ_LAYOUT_* in smj.h)
     uint32_t layouts_off = 0;
     // What the last joins and sorts of a few shapes (relation sizes) learnt
-    // about their payloads (capi.hip device_bucket), least recently used
-    // first out, so a caller alternating shapes on one workspace (sort R,
-    // sort S, join R and S) keeps every shape's:
-    //   mode_hint: the layout the last call reached after leaving the
-    //     narrower ones for its payloads (-2: none), with a re-probe every
-    //     16th call (calls);
-    //   p32_fail: its payloads did not fit 32-bit words, so its calls start at
-    //     the wider layouts (no re-probe: the 32-bit words are for relations
-    //     with tiny payloads, e.g. the sort's).
-    struct ShapeHint {
-        uint64_t shape = ~0ull;
-        int mode_hint = -2;
-        uint32_t calls = 0;
-        bool p32_fail = false;
-        uint64_t used = 0;  // LRU clock
-    };
+    // about their payloads (ShapeHint, layout_policy.hpp), least recently
+    // used first out, so a caller alternating shapes on one workspace (sort R,
+    // sort S, join R and S) keeps every shape's hint
     ShapeHint hints[8];
     uint64_t hint_clock = 0;
     ShapeHint& hint_for(uint64_t shape) {
@@ -330,20 +317,20 @@ uint64_t sampled_capacity(uint64_t n, uint32_t dbits);
 #endif
 constexpr uint32_t kShards = SMJ_SHARDS;
 // Sampled level-1 partition of nrel (1 or 2) relations in shared launches.
-// out[r] holds sampled_capacity() elements: tuples, or (packed, 16-byte tuples
-// only) LayPacked words for host_plan.  When `bad` is given, *bad is OR-ed
-// with kBadPayload (a payload does not pack) and kBadRange (a key lies
-// outside host_plan): packed words need both, tuples are range-checked when
-// the plan was guessed.  `sample` = nrel * 2^dbits counters, zeroed by the
-// caller (k_join_begin).
+// out[r] holds sampled_capacity() elements of `lay` for host_plan (needed by
+// every layout but Tuples; Words and P96: 16-byte tuples only), P48 and P96 in
+// two planes of `pstride` elements.  When `bad` is given, *bad is OR-ed with
+// kBadPayload* (a payload does not pack) and kBadRange (a key lies outside
+// host_plan): packed elements need both, tuples are range-checked when the
+// plan was guessed.  `sample` = nrel * 2^dbits counters, zeroed by the caller
+// (k_join_begin); exact (Tuples, Words): kShards times as many, counted.
 void sampled_partition(Workspace* ws, int nrel, const Tup* const* in, const uint64_t* n,
                        void* const* out, const RangePlan* plan_dev, uint32_t dbits,
                        unsigned int* sample, uint64_t* const* starts_dev,
                        int64_t* const* hist_out, uint64_t* const* seg_start,
                        int64_t* const* seg_cnt, unsigned int* flag_dev, hipStream_t st,
-                       const RangePlan* host_plan = nullptr, bool packed = false,
-                       unsigned int* bad = nullptr, uint64_t p48_stride = 0,
-                       bool p32 = false, bool exact = false, bool p96 = false);
+                       Layout lay, const RangePlan* host_plan, unsigned int* bad,
+                       uint64_t pstride = 0, bool exact = false);
 void hist_memcpy(Workspace* ws, const Tup* in, uint64_t n, Tup* out,
                  uint32_t dbits, hipStream_t st);
 // lane order of LDS atomic returns (k_scatter_swp's ranks): violations, 0 expected
@@ -356,7 +343,7 @@ extern const uint32_t kGroupD3Max;   // widest level-3 digit of the group pass
 struct BucketSortArgs {
     // level-1 partitioned relation(s): bucket b occupies
     // [bstart[b], bstart[b] + bcount[b]) of `part`.
-    const void* part[2];        // tuples, or LayPacked words when `packed`
+    const void* part[2];        // elements of `layout`
     const uint64_t* bstart[2];  // device, nbuckets
     const int64_t* bcount[2];   // device, nbuckets
     // optional (sampled partition): bucket b = kShards segments
@@ -375,13 +362,10 @@ struct BucketSortArgs {
     // the plan, when the host computed it (key-range hints): with a sampled
     // partition the bucket pass then runs without a mid-pipeline host sync
     const RangePlan* host_plan = nullptr;
-    bool packed = false;            // part/tmp hold LayPacked words (host_plan's)
-    // part/tmp hold LayP48 words (packed too): two planes of pstride[r]
-    // elements each (lo uint32, then hi uint16)
-    bool p48 = false;
+    // what part/tmp hold (all but Tuples: packed for host_plan).  P48 (lo
+    // uint32, then hi uint16) and P96: two planes of pstride[r] elements each
+    Layout layout = Layout::Tuples;
     uint64_t pstride[2] = {0, 0};
-    bool p32 = false;  // part/tmp hold LayP32 words (packed too, one plane)
-    bool p96 = false;  // part/tmp hold LayP96 elements (two planes of pstride[r])
     // optional 4-word block zeroed by the caller: [0] = part_flag, [1] =
     // pack_bad, [2] = the skew queue length (read back in one copy)
     unsigned int* status = nullptr;
@@ -410,9 +394,9 @@ struct BucketSortArgs {
 // Returns false (and does nothing) when a->part_flag reports an overflowed
 // sampled partition: the caller repeats the exact partition.
 bool bucket_sort(Workspace* ws, const BucketSortArgs& a, hipStream_t st);
-// smj_tilepass_occupancy (smj.h) of the 48-bit planes' kernel or (p32) the
-// 32-bit words'
-int tilepass_occupancy(bool p32, uint32_t d2);
+// smj_tilepass_occupancy (smj.h) of the 48-bit planes' kernel or the 32-bit
+// words' (-1 for the other layouts)
+int tilepass_occupancy(Layout lay, uint32_t d2);
 
 // plan selection from a device sample (writes plan_dev)
 // (D2 is the size-preferred level-2 width, D2cap the widest the plan may use

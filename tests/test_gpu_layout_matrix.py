@@ -18,8 +18,10 @@ layout the call finished in and (kernel trace) whether the exact partition
 and the skew kernels ran.
 
 The expected layouts are written by hand in the tables, read from
-device_bucket (first_mode, p48_ok, p48_fits, p96_ok, the fallback chain).
-"x!" means: layout x after the exact partition (mode 2: k_hist ran).
+device_bucket (layout_caps, p48_fits) and the ladder it walks
+(csrc/layout_policy.hpp: first_rung, after_void, layout_of); the CPU walk of
+these tables through that header is tests/test_layout_policy.py.
+"x!" means: layout x after the exact partition (rung Exact: k_hist ran).
 
 What the tables had to learn from the code (corrections to the first
 reading; none of them changes a result, only the layout a call ends in):
@@ -29,8 +31,8 @@ reading; none of them changes a result, only the layout a call ends in):
   i % 8 (k_scatter_res).  With fewer than eight workgroups, or a workgroup
   count that is no multiple of eight, the shards are filled unevenly; a shard
   that receives more than its region raises the overflow flag, the attempt's
-  result is discarded and the call goes on to the sampled tuples (mode 1),
-  which overflow likewise, and ends in the exact partition (mode 2, "tuples!").
+  result is discarded and the call goes on to the sampled tuples (rung Sampled),
+  which overflow likewise, and ends in the exact partition (Exact, "tuples!").
   One workgroup (n up to one scatter tile) overflows as soon as a partition
   holds more than about 1190 tuples: 2000 and 2048 tuples at D1 = 0, the sorts
   of 4096 tuples.  A handful of workgroups overflow when partitions are large
@@ -84,7 +86,7 @@ def ceil_log2(x):
 
 
 def choose_levels(n, want_d1, tile=K_TILE_TUPLES):
-    """choose_levels of capi.hip (lines 149-170): (B, D1, D2, D2cap) for a
+    """choose_levels of capi.hip: (B, D1, D2, D2cap) for a
     larger relation of n tuples and fanout_bits want_d1 (0: the default 8)."""
     t = K_GROUP_TARGET
     B = ceil_log2((n + t - 1) // t) if n > t else 0
@@ -98,7 +100,7 @@ def choose_levels(n, want_d1, tile=K_TILE_TUPLES):
 
 
 def make_plan(kmin, kmax, levels, d3max=K_GROUP_D3MAX):
-    """make_plan of smj_common.hpp (lines 997-1020) on choose_levels' result.
+    """make_plan of smj_common.hpp on choose_levels' result.
     Python integers: key_u(kmax) - key_u(kmin) is kmax - kmin."""
     B, D1, D2, D2cap = levels
     width = kmax - kmin if kmax >= kmin else 0
@@ -117,7 +119,7 @@ def make_plan(kmin, kmax, levels, d3max=K_GROUP_D3MAX):
 
 def layout_usable(layout, width, plan, flags, hinted):
     """usable() of the layout (smj_common.hpp) and the conditions device_bucket
-    adds (capi.hip first_mode, p48_ok, p96_ok); tuples always apply."""
+    adds (capi.hip layout_caps); tuples always apply."""
     nb = 1 << plan.D1
     words_ok = hinted and not (flags & (NO_SAMPLED | NO_PACKED)) and plan.D1 <= 10
     if layout == "p32":
@@ -319,7 +321,7 @@ A_ROWS = {
     "device_plan_exact": (SAMPLE_PLAN | NO_SAMPLED, "full", False, "tuples!", "tuples!"),
 }
 # s1 = 0 (empty, one): no packed word (usable() needs s1 >= 1); 16 bytes then
-# take p96 (mode 1, span 0), 8 bytes the sampled tuples
+# take p96 (rung Sampled, span 0), 8 bytes the sampled tuples
 _S1_ZERO = {(8, "empty"): "tuples", (8, "one"): "tuples", (16, "empty"): "p96", (16, "one"): "p96"}
 # A shard region overflows (module docstring) in every sampled attempt:
 #   group  one scatter workgroup, one partition of 2048 tuples
@@ -442,7 +444,7 @@ def group_b():
     # the full 32-bit range (8 B): s1 = 32 at D1 = 0 (tuples), 24 at D1 = 8.
     # There the row ids need 20 bits: not the 8 of a 32-bit word, so the first
     # call goes on to the 48-bit planes and notes p32_fail for the shape.  The
-    # second call skips the 32-bit words in first_mode, and first_mode takes
+    # second call skips the 32-bit words in plan_rung, and plan_rung takes
     # the 48-bit planes only where p48_fits (span < 2^(48 - s1), false here):
     # it runs on the sampled tuples.  Both are right; the layout differs.
     # The sort stays on the 48-bit planes: p48_fits is evaluated once, on the
