@@ -1803,6 +1803,36 @@ void smj_dev_asof_join(smj_workspace* ws, const tuple_t* sortedR, uint64_t nR,
               r_key_out, matched_dev, (hipStream_t)stream);
 }
 
+static_assert(SMJ_OUTER_KEEP_R == kOuterKeepR && SMJ_OUTER_KEEP_S == kOuterKeepS,
+              "smj.h / outerjoin.hip keep bits");
+
+static void check_outer_keep(const char* fn, uint32_t keep) {
+    if (keep & ~(SMJ_OUTER_KEEP_R | SMJ_OUTER_KEEP_S)) {
+        fprintf(stderr, "[ERROR] %s: keep %u has bits other than SMJ_OUTER_KEEP_R | "
+                "SMJ_OUTER_KEEP_S\n", fn, keep);
+        abort();
+    }
+}
+
+uint64_t smj_dev_outer_join(smj_workspace* ws, const tuple_t* sortedR, uint64_t nR,
+                            const tuple_t* sortedS, uint64_t nS, uint32_t keep,
+                            int64_t* r_index_out, int64_t* s_index_out,
+                            value_t* r_payload_out, value_t* s_payload_out, intkey_t* key_out,
+                            uint64_t out_cap, smj_stream_t stream) {
+    check_outer_keep("smj_dev_outer_join", keep);
+    return outer_join((Workspace*)ws, (const Tup*)sortedR, nR, (const Tup*)sortedS, nS, keep,
+                      r_index_out, s_index_out, r_payload_out, s_payload_out, key_out, out_cap,
+                      (hipStream_t)stream);
+}
+
+void smj_dev_outer_join_count(smj_workspace* ws, const tuple_t* sortedR, uint64_t nR,
+                              const tuple_t* sortedS, uint64_t nS, uint32_t keep,
+                              unsigned long long* count_dev, smj_stream_t stream) {
+    check_outer_keep("smj_dev_outer_join_count", keep);
+    outer_join_count((Workspace*)ws, (const Tup*)sortedR, nR, (const Tup*)sortedS, nS, keep,
+                     count_dev, (hipStream_t)stream);
+}
+
 static void check_group_shift(const char* fn, uint32_t group_shift) {
     if (group_shift > 63) {
         fprintf(stderr, "[ERROR] %s: group_shift %u is above 63\n", fn, group_shift);

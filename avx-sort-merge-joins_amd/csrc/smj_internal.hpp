@@ -470,6 +470,22 @@ void asof_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t 
                int64_t* r_index_out, void* r_payload_out, void* r_key_out,
                unsigned long long* matched_dev, hipStream_t st);
 
+// ---- outerjoin.hip : outer join of sorted R and S (smj.h smj_dev_outer_join)
+// The inner join's pairs in join_pairs' order and, in key order between them,
+// the partnerless R tuples (keep & kOuterKeepR) and S tuples (keep &
+// kOuterKeepS; the values of SMJ_OUTER_KEEP_*), as columns: positions in R
+// and S (-1: absent), payloads and key as the ABI's value_t / intkey_t (0:
+// absent); each may be null.  materialize()'s capacity rules; synchronises
+// `st` once, not at all when nR or nS is 0.
+constexpr uint32_t kOuterKeepR = 1, kOuterKeepS = 2;
+uint64_t outer_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
+                    uint32_t keep, int64_t* r_index_out, int64_t* s_index_out,
+                    void* r_payload_out, void* s_payload_out, void* key_out, uint64_t out_cap,
+                    hipStream_t st);
+// its number of rows, added to *count_dev (stream-ordered, no synchronisation)
+void outer_join_count(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
+                      uint32_t keep, unsigned long long* count_dev, hipStream_t st);
+
 // ---- groupagg.hip : grouped aggregation of a sorted relation (smj.h
 // smj_dev_group_aggregate)
 // One row per maximal run of equal key >> group_shift (0..63), in input

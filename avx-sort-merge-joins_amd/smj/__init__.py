@@ -73,12 +73,15 @@ DEVICE_SYMBOLS = [
     "smj_dev_partition_range_shards", "smj_tilepass_occupancy",
     "smj_dev_join_pairs", "smj_dev_semi_join",
     "smj_dev_band_join", "smj_dev_band_join_count", "smj_dev_asof_join",
+    "smj_dev_outer_join", "smj_dev_outer_join_count",
     "smj_dev_group_aggregate", "smj_dev_group_count", "smj_group_tile",
     "smj_workspace_skew_stats",
 ]
 # smj_dev_asof_join's mode (SMJ_ASOF_* in smj.h)
 ASOF_DIRECTIONS = {"backward": 0, "forward": 1, "nearest": 2}
 ASOF_STRICT = 4
+# smj_dev_outer_join's keep (SMJ_OUTER_KEEP_* in smj.h): left preserves R, right S
+OUTER_KEEP = {"inner": 0, "left": 1, "right": 2, "full": 3}
 
 
 def lib_path(width: int) -> str:
@@ -296,6 +299,9 @@ class Library:
             "smj_dev_band_join_count": (None, [_P, _P, _U64, _P, _U64, _I64, _I64, _P, _P]),
             "smj_dev_asof_join": (None, [_P, _P, _U64, _P, _U64, _U32, _U64, _U32, _P, _P, _P,
                                          _P, _P]),
+            "smj_dev_outer_join": (_U64, [_P, _P, _U64, _P, _U64, _U32, _P, _P, _P, _P, _P,
+                                          _U64, _P]),
+            "smj_dev_outer_join_count": (None, [_P, _P, _U64, _P, _U64, _U32, _P, _P]),
             "smj_dev_group_aggregate": (_U64, [_P, _P, _U64, _U32, _P, _P, _P, _P, _P, _P,
                                                _U64, _P]),
             "smj_dev_group_count": (None, [_P, _P, _U64, _U32, _P, _P]),
@@ -923,6 +929,73 @@ class Library:
             self.dev_asof_join(sR, sS, direction, strict, tolerance, group_shift, idx, *cols)
         out = (sS[:, 0].contiguous(), cols[0], idx >= 0)
         return out + (sS[:, 1].contiguous(), cols[1]) if with_keys else out
+
+    @staticmethod
+    def _outer_keep(how):
+        """keep of smj_dev_outer_join, checked here: the library aborts on a
+        value it does not take."""
+        if how not in OUTER_KEEP:
+            raise ValueError(f"how is one of {sorted(OUTER_KEEP)}, not {how!r}")
+        return OUTER_KEEP[how]
+
+    def dev_outer_join(self, sortedR, sortedS, how="full", r_index=None, s_index=None,
+                       r_out=None, s_out=None, key_out=None):
+        """Outer join (smj_dev_outer_join) of two sorted relations: the pairs
+        in dev_join_pairs' order and, in key order between them, the tuples
+        without a partner -- of sortedR with how "left" or "full", of sortedS
+        with "right" or "full" ("inner": none).  Each column given gets the
+        first rows, as many as the shortest of them holds: r_index / s_index
+        (int64) the positions in sortedR / sortedS or -1 for an absent side,
+        r_out / s_out (the payload dtype) the payloads or 0, key_out the key
+        of whichever side is present.  Returns the total; no columns: count
+        only.  Synchronises the current stream at most once."""
+        keep = self._outer_keep(how)
+        cols = [(r_index, "r_index", torch.int64), (s_index, "s_index", torch.int64),
+                (r_out, "r_out", None), (s_out, "s_out", None), (key_out, "key_out", None)]
+        given = [self._group_column(t, what, dt) for t, what, dt in cols if t is not None]
+        cap = builtins_min(t.shape[0] for t in given) if given else 0
+        ptrs = [t.data_ptr() if t is not None and cap else None for t, _, _ in cols]
+        return int(self.lib.smj_dev_outer_join(
+            self.ws, sortedR.data_ptr(), sortedR.shape[0], sortedS.data_ptr(),
+            sortedS.shape[0], keep, *ptrs, cap, self.stream_ptr()))
+
+    def dev_outer_join_count(self, sortedR, sortedS, how, count):
+        """smj_dev_outer_join_count: the outer join's number of rows added to
+        count[0] (int64 device tensor), stream-ordered."""
+        keep = self._outer_keep(how)
+        self._group_column(count, "count", torch.int64)
+        assert count.shape[0] >= 1, "count holds the counter"
+        self.lib.smj_dev_outer_join_count(
+            self.ws, sortedR.data_ptr(), sortedR.shape[0], sortedS.data_ptr(),
+            sortedS.shape[0], keep, count.data_ptr(), self.stream_ptr())
+
+    def outer_join(self, R, S, how="full", key_range=None, with_keys=False):
+        """The outer join of two unsorted device relations in one call: sorts
+        them (dev_join when both hold tuples, dev_sort otherwise) into
+        temporaries, takes the total and returns exactly sized 1-D tensors
+        (r_index, s_index, r_payloads, s_payloads[, keys]) on the current
+        stream, in dev_outer_join's order.  The index columns are positions in
+        the sorted relations and double as the validity mask (>= 0).
+        key_range: an optional (key_min, key_max) hint, as in dev_join."""
+        self._outer_keep(how)
+        dt = torch.int32 if self.width == 8 else torch.int64
+        nR, nS = R.shape[0], S.shape[0]
+        sR, sS = self.empty(nR), self.empty(nS)
+        if nR and nS:
+            count = torch.zeros(1, dtype=torch.int64, device=R.device)
+            kmin, kmax = key_range if key_range is not None else (1, 0)
+            self.dev_join(R, S, sR, sS, count, 10, kmin, kmax)
+        elif nR:
+            self.dev_sort(R, sR)
+        elif nS:
+            self.dev_sort(S, sS)
+        total = self.dev_outer_join(sR, sS, how)
+        cols = [torch.empty(total, dtype=d, device=R.device)
+                for d in (torch.int64, torch.int64, dt, dt) + ((dt,) if with_keys else ())]
+        if total:
+            got = self.dev_outer_join(sR, sS, how, *cols)
+            assert got == total, (got, total)
+        return tuple(cols)
 
     @staticmethod
     def _group_shift(group_shift):

@@ -750,6 +750,60 @@ void smj_dev_asof_join(smj_workspace * ws, const tuple_t * sortedR, uint64_t nR,
                        unsigned long long * matched_dev /* may be NULL */,
                        smj_stream_t stream);
 
+/* Outer join of two sorted relations (non-decreasing keys): the inner join's
+ * pairs and, in key order between them, the tuples without a partner, the
+ * missing side NULL -- one merge, and an output that is still sorted by key
+ * (the library's own; a hash join gives no such order).  NULL is what the
+ * as-of join writes for an unmatched row: -1 in an index column, 0 in a value
+ * column.
+ * keep: 0 is the inner join, SMJ_OUTER_KEEP_R the left outer join with R
+ *   preserved, SMJ_OUTER_KEEP_S the left outer join with S preserved, both
+ *   together the full outer join; any other bit aborts with a message. */
+#define SMJ_OUTER_KEEP_R 1u   /* R tuples without a partner are kept (s side null) */
+#define SMJ_OUTER_KEEP_S 2u   /* S tuples without a partner are kept (r side null) */
+/* Everything below is defined by position in the sorted arrays, so the result
+ *   is deterministic given the inputs (8-byte tie order included).
+ * Order: rows come in ascending order of the union of the keys of R and S, as
+ *   signed keys.  For a key present on both sides the rows are R-major,
+ *   exactly smj_dev_join_pairs' order for that key: for each R tuple of the
+ *   run in sorted order, the whole S run in sorted order.  For a key only in
+ *   R, with SMJ_OUTER_KEEP_R, the rows are the R run in sorted order, one row
+ *   each; without it there are none.  A key only in S likewise with
+ *   SMJ_OUTER_KEEP_S.  With keep == 0 the rows are smj_dev_join_pairs' rows,
+ *   position for position.
+ * Columns: row q has the positions of its tuples in sortedR and sortedS in
+ *   r_index_out[q] and s_index_out[q] (an absent side: -1), their payloads in
+ *   r_payload_out[q] and s_payload_out[q] (an absent side: 0), and its key in
+ *   key_out[q], taken from whichever side is present.  Any subset of the five
+ *   columns may be NULL.
+ * Capacity: the first min(total, out_cap) rows of every non-NULL column are
+ *   written, everything else is left alone, and the total is returned (it may
+ *   exceed 2^32).  out_cap = 0, or all columns NULL, only counts.
+ *   Synchronises `stream` at most once.
+ * Empty calls: nR == 0 && nS == 0 returns 0, launches nothing and does not
+ *   synchronise.  With one side empty the result is 0 rows, or the other
+ *   relation row for row with the empty side null, according to keep (and no
+ *   synchronisation).
+ * Buffers: the inputs are left untouched; the outputs must not overlap them.
+ *   Alignment as for the rest of the device API: tuple-granular slices of a
+ *   hipMalloc buffer (for the 8-byte library also one at an address that is
+ *   8 mod 16), columns aligned to their element. */
+uint64_t smj_dev_outer_join(smj_workspace * ws, const tuple_t * sortedR, uint64_t nR,
+                            const tuple_t * sortedS, uint64_t nS, uint32_t keep,
+                            int64_t * r_index_out   /* may be NULL */,
+                            int64_t * s_index_out   /* may be NULL */,
+                            value_t * r_payload_out /* may be NULL */,
+                            value_t * s_payload_out /* may be NULL */,
+                            intkey_t * key_out      /* may be NULL */,
+                            uint64_t out_cap, smj_stream_t stream);
+
+/* Its number of rows only, ADDED to *count_dev (device), stream-ordered like
+ * smj_dev_band_join_count: no host synchronisation (the workspace's tables
+ * grow on a first call).  The same keep and empty calls. */
+void smj_dev_outer_join_count(smj_workspace * ws, const tuple_t * sortedR, uint64_t nR,
+                              const tuple_t * sortedS, uint64_t nS, uint32_t keep,
+                              unsigned long long * count_dev, smj_stream_t stream);
+
 /* Grouped aggregation of a sorted relation: one output row per group, with
  * the group's first key, where it starts, how many tuples it holds and the
  * sum, minimum and maximum of their payloads (sort-based GROUP BY; the
