@@ -16,6 +16,7 @@
 #include "../../include/smj.h"
 #include "smj_common.hpp"
 #include "smj_internal.hpp"
+#include "partition_policy.hpp"
 
 __global__ void k_setplan(smj::RangePlan* p, smj::RangePlan v) { *p = v; }
 
@@ -1691,6 +1692,20 @@ void smj_workspace_set_layouts(smj_workspace* ws, uint32_t off) {
 
 int smj_workspace_last_layout(smj_workspace* ws) {
     return ((Workspace*)(ws ? ws : smj_context_workspace()))->last_layout;
+}
+
+void smj_workspace_force_ballot_ranks(smj_workspace* ws, int on) {
+    ((Workspace*)(ws ? ws : smj_context_workspace()))->force_ballot_ranks = on != 0;
+}
+
+uint32_t smj_workspace_last_scatter(smj_workspace* ws) {
+    static_assert(scatter_bit(Scatter::Atomic) == SMJ_SCATTER_ATOMIC &&
+                      scatter_bit(Scatter::BallotWc) == SMJ_SCATTER_BALLOT_WC &&
+                      scatter_bit(Scatter::Ballot512x16) == SMJ_SCATTER_BALLOT_512X16 &&
+                      scatter_bit(Scatter::Ballot256x8) == SMJ_SCATTER_BALLOT_256X8 &&
+                      kScatterTwoPass == SMJ_SCATTER_TWO_PASS,
+                  "smj.h / partition_policy.hpp");
+    return ((Workspace*)(ws ? ws : smj_context_workspace()))->last_scatter;
 }
 
 int smj_workspace_skew_stats(smj_workspace* ws, smj_skew_stats* out) {

@@ -27,6 +27,7 @@
 
 #include "smj_common.hpp"
 #include "smj_internal.hpp"
+#include "partition_policy.hpp"
 
 namespace smj {
 
@@ -133,8 +134,7 @@ k_scandig(const uint64_t* __restrict__ totals, uint32_t nbins, int padded,
 //   scr    : 16 uint32
 template <int THREADS, int ITEMS>
 constexpr size_t scatter_lds(uint32_t nbins) {
-    return (size_t)THREADS * ITEMS * sizeof(Tup) + (size_t)nbins * 8 +
-           (size_t)nbins * 4 + (size_t)(THREADS / 64) * nbins * 2 + 64;
+    return scatter_lds_bytes(THREADS, ITEMS, sizeof(Tup), nbins);  // partition_policy.hpp
 }
 
 template <int THREADS, int ITEMS, class Digit>
@@ -277,13 +277,15 @@ struct SwcGeom {
     }
     // stage Tup[TILE] | carry Tup[nbins * (SEG-1)] | run u64[nbins] |
     // tstart, kc, segpre, emit u32[nbins] | wcnt u16[WAVES * nbins] |
-    // segown u16[max_segs] | scan scratch
-    static __host__ __device__ constexpr size_t lds_bytes(uint32_t nbins) {
-        return (size_t)TILE * sizeof(Tup) + (size_t)nbins * (SEG - 1) * sizeof(Tup) +
-               (size_t)nbins * (8 + 4 * 4) + (size_t)WAVES * nbins * 2 +
-               ((size_t)max_segs(nbins) * 2 + 15) / 16 * 16 + 64;
+    // segown u16[max_segs] | scan scratch (the sizes: partition_policy.hpp)
+    static constexpr size_t lds_bytes(uint32_t nbins) {
+        return swc_lds_bytes(THREADS, ITEMS, sizeof(Tup), nbins);
     }
 };
+static_assert(SwcGeom<512, 8>::max_segs(1) == swc_max_segs(512, 8, sizeof(Tup), 1) &&
+                  SwcGeom<512, 8>::max_segs(1024) == swc_max_segs(512, 8, sizeof(Tup), 1024) &&
+                  SwcGeom<512, 8>::max_segs(2048) == swc_max_segs(512, 8, sizeof(Tup), 2048),
+              "partition_policy.hpp sizes segown as the kernel indexes it");
 
 template <int THREADS, int ITEMS, class Digit>
 __global__ void __launch_bounds__(THREADS)
@@ -486,10 +488,9 @@ struct SwaGeom {
     static constexpr uint32_t SEG = SMJ_SWP_SEG / sizeof(Tup);
     static constexpr uint32_t CW = SEG - 1;
     // stage Tup[TILE] | carry Tup[B][CW] | counters u32[W][B/2] | info u32x4[B] |
-    // segown u16[TILE/SEG + 2B] | scan scratch
-    static __host__ __device__ constexpr size_t lds_bytes(uint32_t B) {
-        return (size_t)TILE * sizeof(Tup) + (size_t)B * CW * sizeof(Tup) + (size_t)W * B * 2 +
-               (size_t)B * 16 + ((size_t)(TILE / SEG + 2 * B) * 2 + 15) / 16 * 16 + 128;
+    // segown u16[TILE/SEG + 2B] | scan scratch (the sizes: partition_policy.hpp)
+    static constexpr size_t lds_bytes(uint32_t B) {
+        return swa_lds_bytes(THREADS, ITEMS, sizeof(Tup), B, SMJ_SWP_SEG);
     }
 };
 
@@ -1721,6 +1722,8 @@ static void partition_hist_scatter(Workspace* ws, const Tup* in, uint64_t n,
                                    int64_t* hist_out, int64_t* off_out,
                                    hipStream_t st, const Pack& pk = Pack(),
                                    unsigned int* bad_flag = nullptr) {
+    static_assert(!STABLE || (THREADS == 512 && ITEMS == 16) || (THREADS == 256 && ITEMS == 8),
+                  "the plain ballot scatters of partition_policy.hpp");
     constexpr int TILE = THREADS * ITEMS;
     const uint32_t nbins = 1u << dbits;
     uint64_t ntiles = (n + TILE - 1) / TILE;
@@ -1764,7 +1767,9 @@ static void partition_hist_scatter(Workspace* ws, const Tup* in, uint64_t n,
         // write-combining stable scatter (its own 512x8 geometry; the
         // histogram's chunking, so counts[d][wg] match)
         typedef SwcGeom<512, 8> SG;
-        if (nbins <= 4 * 512 && SG::lds_bytes(nbins) <= 160 * 1024) {
+        const Scatter which = ballot_scatter_choice(dbits, sizeof(Tup));
+        if (which == Scatter::BallotWc) {
+            ws->last_scatter |= scatter_bit(which);
             set_lds_attr((const void*)k_scatter_swc<512, 8, Digit>, 160 * 1024);
             TraceScope ts(ws, "k_scatter", st);
             hipLaunchKernelGGL((k_scatter_swc<512, 8, Digit>), dim3(nwg), dim3(512),
@@ -1773,6 +1778,13 @@ static void partition_hist_scatter(Workspace* ws, const Tup* in, uint64_t n,
             SMJ_CHECK(hipGetLastError());
             return;
         }
+        // (the plain scatter runs on the tiles the caller counted with)
+        if (which != (THREADS == 512 ? Scatter::Ballot512x16 : Scatter::Ballot256x8)) {
+            fprintf(stderr, "[ERROR] smj: stable scatter %d on %d x %d tiles\n", (int)which,
+                    THREADS, ITEMS);
+            abort();
+        }
+        ws->last_scatter |= scatter_bit(which);
         const size_t lds = scatter_lds<THREADS, ITEMS>(nbins);
         set_lds_attr((const void*)k_scatter<THREADS, ITEMS, Digit>, 160 * 1024);
         if (lds > 160 * 1024) {
@@ -1815,7 +1827,7 @@ static void stable_partition_swp(Workspace* ws, const Tup* in, uint64_t n, Tup* 
                                  uint64_t* starts_dev, int64_t* hist_out, int64_t* off_out,
                                  hipStream_t st) {
     constexpr int THREADS = 512;
-    constexpr int ITEMS = sizeof(Tup) == 16 ? 8 : 16;
+    constexpr int ITEMS = swp_items(sizeof(Tup));
     typedef SwaGeom<THREADS, ITEMS> G;
     const uint32_t nbins = 1u << dbits;
     uint64_t ntiles = (n + G::TILE - 1) / G::TILE;
@@ -1848,6 +1860,7 @@ static void stable_partition_swp(Workspace* ws, const Tup* in, uint64_t n, Tup* 
                            starts_dev, hist_out, off_out);
     }
     if (n == 0) return;
+    ws->last_scatter |= scatter_bit(Scatter::Atomic);
     set_lds_attr((const void*)k_scatter_swp<THREADS, ITEMS, Digit, true>, 160 * 1024);
     TraceScope ts(ws, "k_scatter", st);
     hipLaunchKernelGGL((k_scatter_swp<THREADS, ITEMS, Digit, true>), dim3(nwg), dim3(THREADS),
@@ -1862,16 +1875,17 @@ static void stable_partition_narrow(Workspace* ws, const Tup* in, uint64_t n,
                                     int padded, uint64_t* starts_dev,
                                     int64_t* hist_out, int64_t* off_out,
                                     hipStream_t st) {
-    // positions are 32-bit inside k_scatter_swp; its LDS holds 2^10 digits
-    typedef SwaGeom<512, sizeof(Tup) == 16 ? 8 : 16> SG;
-    if (dbits >= 1 && dbits <= 10 && n + ((uint64_t)64 << dbits) < (1ull << 32) &&
-        SG::lds_bytes(1u << dbits) <= 160 * 1024 && lds_order_ok(ws, st)) {
+    // stable_scatter_choice (partition_policy.hpp) decides; the device's
+    // self-check runs only where the atomic ranks would otherwise be taken
+    const bool forced = ws->force_ballot_ranks;
+    Scatter which = stable_scatter_choice(n, dbits, sizeof(Tup), true, forced, SMJ_SWP_SEG);
+    if (which == Scatter::Atomic && !lds_order_ok(ws, st))
+        which = stable_scatter_choice(n, dbits, sizeof(Tup), false, forced, SMJ_SWP_SEG);
+    if (which == Scatter::Atomic)
         stable_partition_swp(ws, in, n, out, dig, dbits, padded, starts_dev, hist_out,
                              off_out, st);
-        return;
-    }
-    // the big tiles need the 16-bit per-wave counters and <= 160 KiB LDS
-    if (dbits <= 10)
+    else if (which != Scatter::Ballot256x8)
+        // (ballot_scatter_choice there: write combining, or plain on these tiles)
         partition_hist_scatter<512, 16, true>(ws, in, n, out, dig, dbits, padded,
                                               starts_dev, hist_out, off_out, st);
     else
@@ -1898,6 +1912,8 @@ void stable_partition(Workspace* ws, const Tup* in, uint64_t n, Tup* out,
                       const Digit32& dig, uint32_t dbits, int padded,
                       int64_t* hist_out, int64_t* off_out, hipStream_t st) {
     const uint32_t nbins = 1u << dbits;
+    // smj_workspace_last_scatter: set where each launch is decided
+    ws->last_scatter = dbits <= kNarrowDigitBits ? 0u : kScatterTwoPass;
     if (dbits <= kNarrowDigitBits) {
         uint64_t* starts = (uint64_t*)ws->scratch("pt_starts", (size_t)nbins * 8);
         stable_partition_narrow(ws, in, n, out, dig, dbits, padded, starts,

@@ -89,6 +89,12 @@ struct Workspace {
         return *victim;
     }
     int last_layout = -1;  // smj_workspace_last_layout (SMJ_LAYOUT_USED_*)
+    // smj_workspace_force_ballot_ranks: the stable partition chooses as on a
+    // device whose LDS atomics fail the lane-order self-check
+    // (partition_policy.hpp); smj_workspace_last_scatter: SMJ_SCATTER_* of
+    // what the last stable_partition launched
+    bool force_ballot_ranks = false;
+    uint32_t last_scatter = 0;
     // smj_workspace_skew_stats: what the skew path of the last completed
     // bucket pass did, in the order of smj_skew_stats (smj.h); host values the
     // pass holds anyway

@@ -75,7 +75,8 @@ DEVICE_SYMBOLS = [
     "smj_dev_band_join", "smj_dev_band_join_count", "smj_dev_asof_join",
     "smj_dev_outer_join", "smj_dev_outer_join_count",
     "smj_dev_group_aggregate", "smj_dev_group_count", "smj_group_tile",
-    "smj_workspace_skew_stats",
+    "smj_workspace_skew_stats", "smj_workspace_force_ballot_ranks",
+    "smj_workspace_last_scatter",
 ]
 # smj_dev_asof_join's mode (SMJ_ASOF_* in smj.h)
 ASOF_DIRECTIONS = {"backward": 0, "forward": 1, "nearest": 2}
@@ -135,6 +136,8 @@ LAYOUT_NO_P48, LAYOUT_NO_PACKED, LAYOUT_NO_SAMPLED, LAYOUT_SAMPLE_PLAN = 1, 2, 4
 LAYOUT_NO_P32, LAYOUT_NO_P96 = 16, 32
 # smj_workspace_last_layout values
 LAYOUTS_USED = ("tuples", "words", "p48", "p32", "p96")
+# smj_workspace_last_scatter bits, lowest first (SMJ_SCATTER_* in smj.h)
+SCATTERS = ("atomic", "ballot-wc", "ballot-512x16", "ballot-256x8", "two-pass")
 # the fields of smj_skew_stats (smj.h), all uint32_t
 SKEW_STATS = ("tpl", "queued", "empty", "small", "large", "items", "inexact", "unordered",
               "resorted", "recounted")
@@ -333,6 +336,8 @@ class Library:
             "smj_workspace_set_layouts": (None, [_P, _U32]),
             "smj_workspace_last_layout": (C.c_int, [_P]),
             "smj_workspace_skew_stats": (C.c_int, [_P, _P]),
+            "smj_workspace_force_ballot_ranks": (None, [_P, C.c_int]),
+            "smj_workspace_last_scatter": (_U32, [_P]),
             "smj_tilepass_occupancy": (C.c_int, [C.c_int, _U32]),
             "smj_trace_enable": (None, [_P, C.c_int]),
             "smj_trace_reset": (None, [_P]),
@@ -650,6 +655,20 @@ class Library:
             return "unknown"
         k = f(None if api else self.ws)
         return LAYOUTS_USED[k] if k >= 0 else "none"
+
+    def force_ballot_ranks(self, on: bool = True):
+        """smj_workspace_force_ballot_ranks on this Library's workspace: its
+        stable partitions choose their scatter as on a device that fails the
+        LDS lane-order self-check (for tests)."""
+        self.lib.smj_workspace_force_ballot_ranks(self.ws, int(bool(on)))
+
+    def last_scatter(self) -> set:
+        """The scatter kernels the last stable partition on this Library's
+        workspace launched (smj_workspace_last_scatter), as a set of SCATTERS
+        names; empty before the first and for a partition of no tuples."""
+        m = int(self.lib.smj_workspace_last_scatter(self.ws))
+        assert m >> len(SCATTERS) == 0, m
+        return {name for i, name in enumerate(SCATTERS) if m >> i & 1}
 
     def skew_stats(self):
         """smj_workspace_skew_stats as a dict (keys SKEW_STATS): what the skew

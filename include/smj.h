@@ -558,6 +558,25 @@ void smj_workspace_set_layouts(smj_workspace * ws, uint32_t off);
 #define SMJ_LAYOUT_USED_P32    3
 #define SMJ_LAYOUT_USED_P96    4
 int smj_workspace_last_layout(smj_workspace * ws);
+/* The stable partition (smj_dev_partition, partition_relation*, radix_cluster)
+ * ranks with lane-ordered LDS atomics where the device passes
+ * smj_selfcheck_lds_order, and with wave ballots where it does not.  on != 0:
+ * the stable partitions on `ws` (NULL: the calling thread's workspace) choose
+ * their scatter kernel as if the device had failed that check; 0 (default):
+ * as the device answers.  The results are the same.  For tests. */
+void smj_workspace_force_ballot_ranks(smj_workspace * ws, int on);
+/* The scatter kernels the last stable partition on `ws` (NULL: the calling
+ * thread's workspace) launched, as a mask: one of the four kernels (DESIGN.md
+ * §3), twice over with SMJ_SCATTER_TWO_PASS for a digit wider than 12 bits;
+ * 0 before the first call, and no kernel's bit for a partition of no tuples.
+ * Set on the host where the launch is decided: no copy and no synchronisation
+ * is added.  For tests. */
+#define SMJ_SCATTER_ATOMIC         1u  /* k_scatter_swp: LDS-atomic ranks */
+#define SMJ_SCATTER_BALLOT_WC      2u  /* k_scatter_swc: ballot ranks, write combining */
+#define SMJ_SCATTER_BALLOT_512X16  4u  /* k_scatter on 512 x 16 tiles */
+#define SMJ_SCATTER_BALLOT_256X8   8u  /* k_scatter on 256 x 8 tiles */
+#define SMJ_SCATTER_TWO_PASS      16u  /* two stable passes and a padding copy */
+uint32_t smj_workspace_last_scatter(smj_workspace * ws);
 /* What became of the groups that the group pass could not finish in LDS and
  * queued for the skew path, in the last bucket pass (the tile and group passes
  * of a device sort or join) that completed on `ws` (NULL: the calling
