@@ -1874,6 +1874,17 @@ void smj_dev_group_count(smj_workspace* ws, const tuple_t* sorted, uint64_t n,
 
 uint32_t smj_group_tile(void) { return group_tile(); }
 
+void smj_dev_window(smj_workspace* ws, const tuple_t* sorted, uint64_t n, uint32_t group_shift,
+                    int64_t* group_out, int64_t* row_out, int64_t* rank_out,
+                    int64_t* dense_rank_out, int64_t* sum_out, value_t* min_out,
+                    value_t* max_out, smj_stream_t stream) {
+    check_group_shift("smj_dev_window", group_shift);
+    window((Workspace*)ws, (const Tup*)sorted, n, group_shift, group_out, row_out, rank_out,
+           dense_rank_out, sum_out, min_out, max_out, (hipStream_t)stream);
+}
+
+uint32_t smj_window_tile(void) { return window_tile(); }
+
 void smj_dev_join(smj_workspace* ws, const tuple_t* R, uint64_t nR,
                   const tuple_t* S, uint64_t nS, tuple_t* sortedR,
                   tuple_t* sortedS, uint32_t fanout_bits, int64_t key_min,

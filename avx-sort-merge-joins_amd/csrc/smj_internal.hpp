@@ -509,6 +509,21 @@ void group_count(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift,
                  unsigned long long* groups_dev, hipStream_t st);
 uint32_t group_tile();  // elements of `in` a workgroup of its kernels handles
 
+// ---- window.hip : window functions over a sorted relation (smj.h
+// smj_dev_window)
+// One row per tuple, PARTITION BY key >> group_shift (0..63) ORDER BY key,
+// ROWS UNBOUNDED PRECEDING, by position in the input: the row of
+// group_aggregate's table that holds the tuple, its position in its group, its
+// rank and dense rank among the group's keys (both from 0), and the running
+// sum (int64, wrapping), minimum and maximum of the payloads from the group's
+// start to it, as columns of int64 / the ABI's value_t (each may be null).
+// Every non-null column gets n rows.  Stream-ordered, no synchronisation;
+// n == 0 or no column launches nothing.
+void window(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift, int64_t* group_out,
+            int64_t* row_out, int64_t* rank_out, int64_t* dense_rank_out, int64_t* sum_out,
+            void* min_out, void* max_out, hipStream_t st);
+uint32_t window_tile();  // elements of `in` a workgroup of its kernels handles
+
 // ---- datagen.hip
 void gen_pk(Tup* out, uint64_t n, uint64_t first, uint64_t total,
             uint64_t seed, hipStream_t st);

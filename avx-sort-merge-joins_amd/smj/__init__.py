@@ -75,6 +75,7 @@ DEVICE_SYMBOLS = [
     "smj_dev_band_join", "smj_dev_band_join_count", "smj_dev_asof_join",
     "smj_dev_outer_join", "smj_dev_outer_join_count",
     "smj_dev_group_aggregate", "smj_dev_group_count", "smj_group_tile",
+    "smj_dev_window", "smj_window_tile",
     "smj_workspace_skew_stats", "smj_workspace_force_ballot_ranks",
     "smj_workspace_last_scatter",
 ]
@@ -309,6 +310,8 @@ class Library:
                                                _U64, _P]),
             "smj_dev_group_count": (None, [_P, _P, _U64, _U32, _P, _P]),
             "smj_group_tile": (_U32, []),
+            "smj_dev_window": (None, [_P, _P, _U64, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
+            "smj_window_tile": (_U32, []),
             "smj_selfcheck_lds_order": (_U64, [_P, _P]),
             "smj_context_workspace": (_P, []),
             "smj_dev_gen_nonunique": (None, [_P, _P, _U64, _U64, _U64, _I64, _U32, _U64, _P]),
@@ -1077,6 +1080,45 @@ class Library:
             got = self.dev_group_aggregate(sT, group_shift, *cols)
             assert got == groups, (got, groups)
         return tuple(cols)
+
+    def dev_window(self, sorted, group_shift=0, group=None, row=None, rank=None,
+                   dense_rank=None, sum=None, min=None, max=None):
+        """Window functions (smj_dev_window): one row per tuple of `sorted`,
+        PARTITION BY (key >> group_shift) ORDER BY key, ROWS UNBOUNDED
+        PRECEDING.  Each column given gets len(sorted) rows: group (the row of
+        dev_group_aggregate's table that holds the tuple), row (its position
+        in its group), rank and dense_rank (among the group's keys, from 0)
+        and sum (of the payloads from the group's start to it, wrapping) in
+        int64, min / max (of those payloads) in the payload dtype.
+        Stream-ordered: no synchronisation."""
+        gsh = self._group_shift(group_shift)
+        n = sorted.shape[0]
+        cols = [(group, "group", torch.int64), (row, "row", torch.int64),
+                (rank, "rank", torch.int64), (dense_rank, "dense_rank", torch.int64),
+                (sum, "sum", torch.int64), (min, "min", None), (max, "max", None)]
+        for t, what, dt in cols:
+            if t is not None:
+                assert self._group_column(t, what, dt).shape[0] == n, what
+        ptrs = [t.data_ptr() if t is not None and n else None for t, _, _ in cols]
+        self.lib.smj_dev_window(self.ws, sorted.data_ptr(), n, gsh, *ptrs, self.stream_ptr())
+
+    def window_tile(self):
+        """Elements one workgroup of the window kernels handles (a host call)."""
+        return int(self.lib.smj_window_tile())
+
+    def window(self, T, group_shift=0):
+        """The window functions of an unsorted device relation in one call:
+        sorts it (dev_sort) into a temporary and returns (sorted, group, row,
+        rank, dense_rank, sum, min, max), exactly sized, on the current
+        stream; row i of every column belongs to sorted[i]."""
+        dt = torch.int32 if self.width == 8 else torch.int64
+        n = T.shape[0]
+        sT = self.empty(n, device=T.device)
+        cols = [torch.empty(n, dtype=d, device=T.device) for d in (torch.int64,) * 5 + (dt, dt)]
+        if n:
+            self.dev_sort(T, sT)
+            self.dev_window(sT, group_shift, *cols)
+        return (sT, *cols)
 
     def dev_join(self, R, S, sortedR, sortedS, count, fanout_bits=10,
                  key_min=1, key_max=0):

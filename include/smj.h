@@ -872,6 +872,55 @@ void smj_dev_group_count(smj_workspace * ws, const tuple_t * sorted, uint64_t n,
  * a host call, no device needed). */
 uint32_t smj_group_tile(void);
 
+/* Window functions over a sorted relation: one output row per tuple, the SQL
+ * window functions over PARTITION BY key >> group_shift ORDER BY key with the
+ * frame ROWS UNBOUNDED PRECEDING (the library's own).  Defined by position in
+ * the input and total: there is no undefined input.
+ * Heads: with g(i) = key[i] >> group_shift (an arithmetic shift of the key
+ *   widened to int64; group_shift 0..63, values above 63 abort with a
+ *   message), element i is a group head when i == 0 or g(i) != g(i-1), and a
+ *   key head when i == 0 or key[i] != key[i-1].  Every group head is a key
+ *   head.  h(i) is the last group head at or before i, p(i) the last key head
+ *   at or before i.  On a relation with non-decreasing keys this is the SQL
+ *   meaning; on any other input it is the run-length form: keys 1,1,2,1 give
+ *   three groups.
+ * Rows: every non-NULL column gets all n rows; row i belongs to sorted[i].
+ *   group_out[i]      = the group heads in [0, i], minus 1: the row of
+ *                       smj_dev_group_aggregate's table that holds i's group
+ *                       (whole-group totals per tuple are a gather of that
+ *                       table with this column).
+ *   row_out[i]        = i - h(i)                 (ROW_NUMBER() - 1).
+ *   rank_out[i]       = p(i) - h(i)              (RANK() - 1, ordered by key).
+ *   dense_rank_out[i] = the key heads in (h(i), i]      (DENSE_RANK() - 1).
+ *   sum_out[i]        = the sum of the payloads of sorted[h(i) .. i] as int64
+ *                       modulo 2^64 (the 8-byte library sign-extends its int32
+ *                       payloads first).
+ *   min_out[i], max_out[i] = their signed minimum and maximum.
+ *   Peers with equal keys do not share a value.  With group_shift == 0, rank
+ *   and dense_rank are 0 everywhere (defined, not an error).
+ * Output: nothing is written beyond row n - 1.  n == 0, or all seven columns
+ *   NULL, launches nothing.  Stream-ordered like smj_dev_asof_join: no host
+ *   synchronisation (the workspace's tables grow on a first call).
+ * Buffers: the input is left untouched; the outputs must not overlap it or
+ *   each other.  Alignment as for the rest of the device API: any
+ *   tuple-granular slice of a hipMalloc buffer (for the 8-byte library also
+ *   one at an address that is 8 mod 16), columns aligned to their element.
+ *   n may exceed 2^32. */
+void smj_dev_window(smj_workspace * ws, const tuple_t * sorted, uint64_t n,
+                    uint32_t group_shift,
+                    int64_t * group_out      /* may be NULL */,
+                    int64_t * row_out        /* may be NULL */,
+                    int64_t * rank_out       /* may be NULL */,
+                    int64_t * dense_rank_out /* may be NULL */,
+                    int64_t * sum_out        /* may be NULL */,
+                    value_t * min_out        /* may be NULL */,
+                    value_t * max_out        /* may be NULL */,
+                    smj_stream_t stream);
+
+/* Elements of `sorted` one workgroup of the window kernels handles (for
+ * tests; a host call, no device needed). */
+uint32_t smj_window_tile(void);
+
 /* The m-way join on one device.  R and S are left untouched; sortedR/sortedS
  * (n tuples each) receive the fully sorted relations; the match count is
  * written to *count_dev.  key_min <= key_max is an optional hint of the key
