@@ -1717,6 +1717,22 @@ int smj_workspace_skew_stats(smj_workspace* ws, smj_skew_stats* out) {
     return 0;
 }
 
+int smj_workspace_merge_stats(smj_workspace* ws, smj_merge_stats* out) {
+    static_assert(kMergeNone == SMJ_MERGE_NONE && kMergeBuckets == SMJ_MERGE_BUCKETS &&
+                      kMergeTree == SMJ_MERGE_TREE,
+                  "smj.h / smj_internal.hpp");
+    const Workspace* w = (Workspace*)(ws ? ws : smj_context_workspace());
+    if (!w->merge_valid) return -1;
+    const Workspace::MergeStats& m = w->merge;
+    uint32_t queued = 0;
+    // the one copy: the queue's length, written by the merge's kernels (the
+    // caller has synchronised the merge's stream)
+    if (m.form == kMergeBuckets)
+        SMJ_CHECK(hipMemcpy(&queued, m.queue, sizeof queued, hipMemcpyDeviceToHost));
+    *out = smj_merge_stats{m.form, m.k, m.D, queued};
+    return 0;
+}
+
 int smj_tilepass_occupancy(int layout, uint32_t d2_bits) {
     return tilepass_occupancy((Layout)layout, d2_bits);
 }

@@ -649,7 +649,10 @@ k_km_merge(const KmRun* __restrict__ runs, uint32_t k, uint32_t D,
     // bucket's key offset, its top KM_LOGNB bits (exact keys for buckets no
     // wider than KM_NB keys)
     const uint32_t s = km_shift(mm[0], mm[1], D);
-    const uint64_t base = mm[0] + ((uint64_t)b << s);
+    // (s = 64 only with D = 0, one bucket over the full 64-bit key range: b is
+    // 0 there, so the shift amount taken modulo 64 gives the same base and
+    // stays defined)
+    const uint64_t base = mm[0] + ((uint64_t)b << (s & 63));
     const uint32_t s3 = s > KM_LOGNB ? s - KM_LOGNB : 0;
     Tup v[KM_IPT];
     uint32_t dg[KM_IPT];
@@ -875,6 +878,8 @@ static bool multiway_merge_buckets(Workspace* ws, const Tup* const* runs, const 
     hipLaunchKernelGGL(k_km_over, dim3(B < 64 ? B : 64), dim3(KM_THREADS), 0, st, dr, k, D, off,
                        q, out);
     SMJ_CHECK(hipGetLastError());
+    ws->merge = Workspace::MergeStats{kMergeBuckets, k, D, q};
+    ws->merge_valid = true;
     return true;
 }
 
@@ -885,6 +890,10 @@ void multiway_merge(Workspace* ws, const Tup* const* runs, const uint64_t* lens,
                     uint32_t k, Tup* out, hipStream_t st) {
     uint64_t total = 0;
     for (uint32_t i = 0; i < k; i++) total += lens[i];
+    // smj_workspace_merge_stats: the form decided here (the one-pass form
+    // adds its bucket bits and its queue)
+    ws->merge = Workspace::MergeStats{total ? kMergeTree : kMergeNone, k, 0, nullptr};
+    ws->merge_valid = true;
     if (total == 0) return;
     if (multiway_merge_buckets(ws, runs, lens, k, total, out, st)) return;
     multiway_merge_tree(ws, runs, lens, k, out, st);

@@ -104,6 +104,16 @@ struct Workspace {
     };
     SkewStats skew;
     bool skew_valid = false;
+    // smj_workspace_merge_stats: what the last multiway_merge decided (host
+    // values: form SMJ_MERGE_* of smj.h, runs, bucket bits) and the overflow
+    // queue its one-pass form used (word 0, the queue's length, is read by the
+    // accessor, not by the merge)
+    struct MergeStats {
+        uint32_t form = 0, k = 0, D = 0;
+        const unsigned int* queue = nullptr;
+    };
+    MergeStats merge;
+    bool merge_valid = false;
     std::map<std::string, std::pair<void*, size_t>> bufs;
     std::map<std::string, std::pair<void*, size_t>> pinned;
     // the k-way merge's run table as last uploaded, and where (a repeated
@@ -423,6 +433,8 @@ void merge_join_count(const Tup* r, uint64_t nr, const Tup* s, uint64_t ns,
 void merge_join_count_batch(Workspace* ws, const Tup* const* r, const uint64_t* nr,
                             const Tup* const* s, const uint64_t* ns, uint32_t k,
                             unsigned long long* count_dev, hipStream_t st);
+// Workspace::merge.form (SMJ_MERGE_* of smj.h; capi.hip asserts the match)
+constexpr uint32_t kMergeNone = 0, kMergeBuckets = 1, kMergeTree = 2;
 void multiway_merge(Workspace* ws, const Tup* const* runs_host,
                     const uint64_t* lens_host, uint32_t k, Tup* out,
                     hipStream_t st);

@@ -77,7 +77,7 @@ DEVICE_SYMBOLS = [
     "smj_dev_group_aggregate", "smj_dev_group_count", "smj_group_tile",
     "smj_dev_window", "smj_window_tile",
     "smj_workspace_skew_stats", "smj_workspace_force_ballot_ranks",
-    "smj_workspace_last_scatter",
+    "smj_workspace_last_scatter", "smj_workspace_merge_stats",
 ]
 # smj_dev_asof_join's mode (SMJ_ASOF_* in smj.h)
 ASOF_DIRECTIONS = {"backward": 0, "forward": 1, "nearest": 2}
@@ -142,6 +142,9 @@ SCATTERS = ("atomic", "ballot-wc", "ballot-512x16", "ballot-256x8", "two-pass")
 # the fields of smj_skew_stats (smj.h), all uint32_t
 SKEW_STATS = ("tpl", "queued", "empty", "small", "large", "items", "inexact", "unordered",
               "resorted", "recounted")
+# smj_merge_stats.form (SMJ_MERGE_* in smj.h) and its fields, all uint32_t
+MERGE_FORMS = ("none", "buckets", "tree")
+MERGE_STATS = ("form", "k", "D", "queued")
 # smj_mgpu_join flags (include/smj.h)
 MG_COPY, MG_NOPLANES, MG_ONECALL, MG_SAMPLED, MG_EXACT = 1, 2, 4, 8, 16
 MG_LAYOUTS = ("tuples", "words", "planes")
@@ -341,6 +344,7 @@ class Library:
             "smj_workspace_skew_stats": (C.c_int, [_P, _P]),
             "smj_workspace_force_ballot_ranks": (None, [_P, C.c_int]),
             "smj_workspace_last_scatter": (_U32, [_P]),
+            "smj_workspace_merge_stats": (C.c_int, [_P, _P]),
             "smj_tilepass_occupancy": (C.c_int, [C.c_int, _U32]),
             "smj_trace_enable": (None, [_P, C.c_int]),
             "smj_trace_reset": (None, [_P]),
@@ -681,6 +685,18 @@ class Library:
         if self.lib.smj_workspace_skew_stats(self.ws, out) != 0:
             return None
         return dict(zip(SKEW_STATS, (int(v) for v in out)))
+
+    def merge_stats(self):
+        """smj_workspace_merge_stats as a dict (keys MERGE_STATS, form as a
+        MERGE_FORMS name): what the last k-way merge on this Library's
+        workspace did; None before the first.  Reads the overflow queue's
+        length with a blocking copy: synchronise the merge's stream first."""
+        out = (C.c_uint32 * len(MERGE_STATS))()
+        if self.lib.smj_workspace_merge_stats(self.ws, out) != 0:
+            return None
+        d = dict(zip(MERGE_STATS, (int(v) for v in out)))
+        d["form"] = MERGE_FORMS[d["form"]]
+        return d
 
     def tilepass_occupancy(self, layout: str = "p48", d2_bits: int = 10) -> int:
         """smj_tilepass_occupancy: workgroups of the tile-pass kernel of

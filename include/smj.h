@@ -599,6 +599,25 @@ typedef struct smj_skew_stats {
     uint32_t recounted;  /* pairs handed to the batched merge-join count */
 } smj_skew_stats;
 int smj_workspace_skew_stats(smj_workspace * ws, smj_skew_stats * out);
+/* What the last k-way merge (smj_dev_multiway_merge_host, avx_multiway_merge
+ * and whatever else merges k runs) on `ws` (NULL: the calling thread's
+ * workspace) did.  form, k and D are host values, stored where the merge
+ * chooses its form.  queued is word 0 of the merge's overflow queue on the
+ * device, read here with one blocking copy: the caller must have synchronised
+ * the merge's stream before the call, and this accessor is the only place a
+ * copy is added -- none to the merge itself.  For tests.  Returns 0, or -1
+ * (and leaves *out) before the first k-way merge on the workspace. */
+#define SMJ_MERGE_NONE    0u  /* no tuples: nothing launched */
+#define SMJ_MERGE_BUCKETS 1u  /* 3..256 runs: one pass over 2^D value buckets */
+#define SMJ_MERGE_TREE    2u  /* 1, 2 or more than 256 runs: 2-way merge passes */
+typedef struct smj_merge_stats {
+    uint32_t form;    /* SMJ_MERGE_* */
+    uint32_t k;       /* runs, empty ones included */
+    uint32_t D;       /* SMJ_MERGE_BUCKETS: bucket bits, else 0 */
+    uint32_t queued;  /* SMJ_MERGE_BUCKETS: buckets larger than the LDS buffer,
+                         merged by the overflow kernel; else 0 */
+} smj_merge_stats;
+int smj_workspace_merge_stats(smj_workspace * ws, smj_merge_stats * out);
 /* Workgroups of the tile-pass kernel that intermediate layout `layout`
  * (SMJ_LAYOUT_USED_P48 or _P32) takes which the runtime places on one compute
  * unit (hipOccupancyMaxActiveBlocksPerMultiprocessor) at the dynamic LDS size
@@ -624,7 +643,10 @@ void smj_dev_partition(smj_workspace * ws, const tuple_t * in, uint64_t n,
 void smj_dev_sort(smj_workspace * ws, const tuple_t * in, uint64_t n,
                   tuple_t * out, smj_stream_t stream);
 
-/* Merge two sorted runs. */
+/* Merge two sorted runs.  The call takes no workspace: its tile table lies in
+ * the calling thread's workspace, whatever `stream` is, so like `ws`
+ * elsewhere it serves one stream at a time -- two streams of one thread would
+ * share that table. */
 void smj_dev_merge2(const tuple_t * a, uint64_t na, const tuple_t * b,
                     uint64_t nb, tuple_t * out, smj_stream_t stream);
 
