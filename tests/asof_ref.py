@@ -7,11 +7,14 @@ column of R (-1: none).  With lb / ub the searchsorted positions of the S key
 ("left" / "right"), the candidates are B = ub - 1 and F = lb, or B = lb - 1
 and F = ub when strict; each is filtered by the tolerance and the group, and
 nearest takes the survivor at the smaller distance, B on equal distances.
-Distances and shifts are taken on Python integers, so nothing wraps around.
+Distances and shifts are taken on Python integers, so nothing wraps around
+(numpy_asof_exact), or, where every |key| is below 2^62 and nothing can wrap,
+in int64 over the whole column at once (numpy_asof_fast).
 double_loop is the plain definition: a scan of all of R per S tuple.
 """
 import numpy as np
 
+from band_ref import max_abs
 from test_gpu_band_join import saturate
 from test_gpu_parity import rand_tuples
 
@@ -19,8 +22,59 @@ DIRECTIONS = ("backward", "forward", "nearest")
 MODES = [(d, s) for d in DIRECTIONS for s in (False, True)]   # the 6 mode combinations
 
 
+FAST_LIMIT = 1 << 62
+
+
+def fast_ok(Rk, Sk):
+    """No difference of two keys can leave int64: the precondition of
+    numpy_asof_fast."""
+    return max_abs(np.asarray(Rk), np.asarray(Sk)) < FAST_LIMIT
+
+
 def numpy_asof(Rk, Sk, direction="backward", strict=False, tolerance=None, group_shift=0):
-    """int64 r_idx per S row into the sorted key array Rk, -1 for none."""
+    """int64 r_idx per S row into the sorted key array Rk, -1 for none:
+    numpy_asof_fast where its precondition holds (test_blocks_cases.py pins it
+    to the exact path), numpy_asof_exact otherwise."""
+    fn = numpy_asof_fast if fast_ok(Rk, Sk) else numpy_asof_exact
+    return fn(Rk, Sk, direction, strict, tolerance, group_shift)
+
+
+def numpy_asof_fast(Rk, Sk, direction="backward", strict=False, tolerance=None, group_shift=0):
+    """numpy_asof with the distances taken in int64, for a million S tuples
+    at a time; only where max |key| < 2^62, so no difference wraps."""
+    assert direction in DIRECTIONS and fast_ok(Rk, Sk)
+    Rk, Sk = np.asarray(Rk, np.int64), np.asarray(Sk, np.int64)
+    nR, nS = len(Rk), len(Sk)
+    none = np.full(nS, -1, np.int64)
+    if nR == 0 or nS == 0:
+        return none
+    lb, ub = np.searchsorted(Rk, Sk, "left"), np.searchsorted(Rk, Sk, "right")
+    b = (lb if strict else ub) - 1   # -1: no B
+    f = ub if strict else lb         # nR: no F
+    # a distance is below 2^63: a larger tolerance is no limit
+    tol = None if tolerance is None or tolerance >= 1 << 63 else np.int64(tolerance)
+
+    def side(pos, there):
+        r = Rk[np.where(there, pos, 0)]
+        dist = np.where(there, np.abs(Sk - r), 0)
+        ok = there.copy()
+        if tol is not None:
+            ok &= dist <= tol
+        if group_shift:
+            ok &= (r >> group_shift) == (Sk >> group_shift)
+        return ok, dist
+
+    okb, db = side(b, b >= 0)
+    okf, df = side(f, f < nR)
+    if direction == "backward":
+        return np.where(okb, b, none)
+    if direction == "forward":
+        return np.where(okf, f, none)
+    return np.where(okb & (~okf | (db <= df)), b, np.where(okf, f, none))
+
+
+def numpy_asof_exact(Rk, Sk, direction="backward", strict=False, tolerance=None, group_shift=0):
+    """numpy_asof with the distances and shifts taken on Python integers."""
     assert direction in DIRECTIONS
     Rk, Sk = np.asarray(Rk, np.int64), np.asarray(Sk, np.int64)
     nR, nS = len(Rk), len(Sk)

@@ -466,7 +466,8 @@ def sorted_pair(orc, width, nR, nS):
 
 def family(f):
     """R and S at odd offsets, over the sizes that cross MT_TILE = 512,
-    MT_RWIN, the 1024-element scan blocks and kMatPiece."""
+    MT_RWIN = 1024 and kMatPiece = 8192.  At most 137 S tiles: the scan's
+    blocks of 1024 tiles are test_gpu_join_blocks.py's."""
     f = pytest.mark.parametrize("offR,offS", [(1, 0), (0, 1), (1, 1)])(f)
     return pytest.mark.parametrize("nR,nS", [(1, 1), (1025, 2049), (40_001, 70_001)])(f)
 
