@@ -28,8 +28,8 @@
 //                 thread i of each round reads element i's partner tuple from
 //                 R and writes row tb + i of every column (coalesced), and
 //                 the tile's matched rows go to a table;
-//   k_asof_total  the table summed into *matched_dev, one atomic per 1024
-//                 tiles (only when the caller asks for the count).
+//   k_asof_total  the table summed into *matched_dev by materialize.hip's
+//                 tile_total (only when the caller asks for the count).
 #include "smj_common.hpp"
 #include "smj_internal.hpp"
 #include "mat_common.hpp"
@@ -118,14 +118,6 @@ __device__ __forceinline__ uint32_t asof_partners(K rkey, uint64_t Rlo, uint64_t
     return matched;
 }
 
-__device__ __forceinline__ void st_idx(int64_t* p, int64_t v) {
-#if SMJ_NT_STORES
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-
 // tile_out null: the caller does not ask for the matched count
 __global__ void __launch_bounds__(MT_THREADS)
 k_asof_tile(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
@@ -136,20 +128,16 @@ k_asof_tile(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
     const uint64_t tb = (uint64_t)blockIdx.x * MT_TILE;
     const uint32_t len = (uint32_t)min((uint64_t)MT_TILE, nS - tb);
     const uint64_t Rlo = bounds[2 * blockIdx.x], W = bounds[2 * blockIdx.x + 1] - Rlo;
-    for (uint32_t i = tid; i < len; i += MT_THREADS) L.key[i] = tup_key(S[tb + i]);
-    const bool staged = W <= MT_RWIN;  // uniform over the workgroup
-    if (staged)
-        for (uint32_t i = tid; i < W; i += MT_THREADS) L.rkey[i] = tup_key(R[Rlo + i]);
+    stage_s_keys(S, tb, len, L.key);
+    const bool staged = stage_r_window(R, Rlo, W, L.rkey);
     __syncthreads();
     const uint32_t i0 = tid * MT_IPT;
-    uint32_t matched;
-    if (staged) {
-        const int64_t* rk = L.rkey;
-        matched = asof_partners([rk](uint64_t i) { return rk[i]; }, Rlo, W, L.key, i0, len, m);
-    } else {
-        const Tup* rw = R + Rlo;
-        matched = asof_partners(TupKey{rw}, Rlo, W, L.key, i0, len, m);
-    }
+    uint32_t matched = 0;
+    with_window(staged, L.rkey, R, Rlo, [&](auto rk) {
+        matched = asof_partners(rk, Rlo, W, L.key, i0, len, m);
+    });
+    // the tile's sum shares its barrier with the partners' hand-over, so it
+    // is not mat_common.hpp's tile_reduce_store (which brings its own)
     if (tile_out) {
         matched = wave_sum(matched);
         if (lane_id() == 0) L.wsum[tid >> 6] = matched;
@@ -170,27 +158,9 @@ k_asof_tile(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
             pay = mat_payload(&r);
             key = (MatVal)tup_key(r);
         }
-        if (cols.idx) st_idx(cols.idx + tb + i, q);
-        if (cols.pay) st_val(cols.pay + tb + i, pay);
-        if (cols.key) st_val(cols.key + tb + i, key);
-    }
-}
-
-// the tiles' matched rows added to *total, one atomic per 1024 tiles
-// (k_band_total's reduction, over 32-bit counts)
-constexpr uint32_t AT_BLOCK = 1024;
-
-__global__ void __launch_bounds__(AT_BLOCK)
-k_asof_total(const uint32_t* __restrict__ cnt, uint64_t ntiles, unsigned long long* total) {
-    __shared__ uint64_t ws[AT_BLOCK / 64];
-    const uint64_t t = (uint64_t)blockIdx.x * AT_BLOCK + threadIdx.x;
-    const uint64_t c = wave_sum((uint64_t)(t < ntiles ? cnt[t] : 0));
-    if (lane_id() == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t a = 0;
-        for (uint32_t w = 0; w < AT_BLOCK / 64; w++) a += ws[w];
-        if (a) atomicAdd(total, (unsigned long long)a);
+        if (cols.idx) st_col(cols.idx + tb + i, q);
+        if (cols.pay) st_col(cols.pay + tb + i, pay);
+        if (cols.key) st_col(cols.key + tb + i, key);
     }
 }
 
@@ -205,25 +175,16 @@ void asof_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t 
     uint64_t* bounds = (uint64_t*)ws->scratch("asof_tab", ntiles * (2 * 8 + 4));
     uint32_t* tile_cnt = matched_dev ? (uint32_t*)(bounds + 2 * ntiles) : nullptr;
     const AsofMode m{dir, strict ? 1u : 0u, group_shift, tolerance};
-    {
-        // nR == 0: every window is empty and no element finds a candidate
-        TraceScope ts(ws, "k_asof_bounds", st);
-        hipLaunchKernelGGL(k_asof_bounds, dim3((uint32_t)((ntiles + 255) / 256)), dim3(256), 0,
-                           st, R, nR, S, nS, ntiles, bounds);
-        SMJ_CHECK(hipGetLastError());
-    }
+    // nR == 0: every window is empty and no element finds a candidate
+    launch_tile_bounds(ws, "k_asof_bounds", k_asof_bounds, ntiles, st, R, nR, S, nS, ntiles,
+                       bounds);
     {
         TraceScope ts(ws, "k_asof_tile", st);
         hipLaunchKernelGGL(k_asof_tile, dim3((uint32_t)ntiles), dim3(MT_THREADS), 0, st, R, S, nS,
                            bounds, m, cols, tile_cnt);
         SMJ_CHECK(hipGetLastError());
     }
-    if (matched_dev) {
-        TraceScope ts(ws, "k_asof_total", st);
-        hipLaunchKernelGGL(k_asof_total, dim3((uint32_t)((ntiles + AT_BLOCK - 1) / AT_BLOCK)),
-                           dim3(AT_BLOCK), 0, st, tile_cnt, ntiles, matched_dev);
-        SMJ_CHECK(hipGetLastError());
-    }
+    if (matched_dev) tile_total(ws, "k_asof_total", tile_cnt, ntiles, matched_dev, st);
 }
 
 }  // namespace smj

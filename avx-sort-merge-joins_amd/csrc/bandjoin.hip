@@ -114,6 +114,9 @@ __device__ __forceinline__ void band_tile(const Tup* __restrict__ R,
                                           uint64_t W, uint64_t tb, uint32_t len, int64_t lo,
                                           int64_t hi, BandLDS& L, uint64_t (&start)[MT_IPT],
                                           uint64_t (&cnt)[MT_IPT]) {
+    // mat_common.hpp's stage_s_keys / stage_r_window / with_window written out:
+    // through the helpers k_band_count took 32 VGPRs for 30 and measured 0.5 %
+    // slower
     const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < len; i += MT_THREADS) L.key[i] = tup_key(S[tb + i]);
     const bool staged = W <= MT_RWIN;
@@ -121,13 +124,8 @@ __device__ __forceinline__ void band_tile(const Tup* __restrict__ R,
         for (uint32_t i = tid; i < W; i += MT_THREADS) L.rkey[i] = tup_key(R[Rlo + i]);
     __syncthreads();
     const uint32_t i0 = tid * MT_IPT;
-    if (staged) {
-        const int64_t* rk = L.rkey;
-        band_ranges([rk](uint64_t i) { return rk[i]; }, W, L.key, i0, len, lo, hi, start, cnt);
-    } else {
-        const Tup* rw = R + Rlo;
-        band_ranges(TupKey{rw}, W, L.key, i0, len, lo, hi, start, cnt);
-    }
+    if (staged) band_ranges(LdsKey{L.rkey}, W, L.key, i0, len, lo, hi, start, cnt);
+    else band_ranges(TupKey{R + Rlo}, W, L.key, i0, len, lo, hi, start, cnt);
 }
 
 // ent null: a count-only call, nothing will read the entries
@@ -149,31 +147,7 @@ k_band_count(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS, 
         if (ent && !band_wide(W) && i0 + p < len)
             ent[tb + i0 + p] = make_uint2((uint32_t)start[p], (uint32_t)cnt[p]);
     }
-    s = wave_sum(s);
-    if (lane_id() == 0) L.wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t t = 0;
-        for (int w = 0; w < MT_THREADS / 64; w++) t += L.wsum[w];
-        tile_out[blockIdx.x] = t;
-    }
-}
-
-// the count form: the tile sums added to *total, one atomic per 1024 tiles
-constexpr uint32_t BT_BLOCK = 1024;
-
-__global__ void __launch_bounds__(BT_BLOCK)
-k_band_total(const uint64_t* __restrict__ cnt, uint64_t ntiles, unsigned long long* total) {
-    __shared__ uint64_t ws[BT_BLOCK / 64];
-    const uint64_t t = (uint64_t)blockIdx.x * BT_BLOCK + threadIdx.x;
-    const uint64_t c = wave_sum(t < ntiles ? cnt[t] : 0);
-    if (lane_id() == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t a = 0;
-        for (uint32_t w = 0; w < BT_BLOCK / 64; w++) a += ws[w];
-        if (a) atomicAdd(total, (unsigned long long)a);
-    }
+    tile_reduce_store(s, L.wsum, tile_out);
 }
 
 __global__ void __launch_bounds__(MT_THREADS)
@@ -186,24 +160,10 @@ k_band_write(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS, 
     __shared__ uint64_t pre[MT_TILE];  // inclusive prefix of the range lengths
     __shared__ uint64_t beg[MT_TILE];  // range starts in the window
     __shared__ uint64_t sh_t;
-    const uint64_t w = blockIdx.x;
-    if (threadIdx.x == 0) {
-        // the last tile whose first item is <= w owns item w
-        uint64_t a = 0, b = ntiles;
-        while (a < b) {
-            const uint64_t m = (a + b) >> 1;
-            if (ibase[m] <= w) a = m + 1; else b = m;
-        }
-        sh_t = a - 1;
-    }
-    __syncthreads();
-    const uint64_t t = sh_t;
-    const uint64_t q0 = (w - ibase[t]) * kMatPiece;
-    const uint64_t q1 = min(q0 + kMatPiece, cnt[t]);
-    const uint64_t ob = base[t];
-    if (ob + q0 >= out_cap) return;  // uniform over the workgroup
-    const uint64_t tb = t * MT_TILE;
-    const uint32_t len = (uint32_t)min((uint64_t)MT_TILE, nS - tb);
+    const MatPiece pc = mat_piece(ibase, cnt, base, ntiles, nS, out_cap, &sh_t);
+    if (!pc.live) return;
+    const uint64_t t = pc.t, q0 = pc.q0, q1 = pc.q1, ob = pc.ob, tb = pc.tb;
+    const uint32_t len = pc.len;
     const uint64_t Rlo = bounds[2 * t], W = bounds[2 * t + 1] - Rlo;
     const uint32_t i0 = threadIdx.x * MT_IPT;
     uint64_t start[MT_IPT], c[MT_IPT];
@@ -234,45 +194,24 @@ k_band_write(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS, 
     for (uint64_t q = q0 + threadIdx.x; q < q1; q += MT_THREADS) {
         if (ob + q >= out_cap) break;
         // element j: the first inclusive prefix above q (q < cnt[t] = pre[len - 1])
-        uint32_t a = 0, b = len - 1;
-        while (a < b) {
-            const uint32_t m = (a + b) >> 1;
-            if (pre[m] <= q) a = m + 1; else b = m;
-        }
-        const uint32_t j = a;
+        const uint32_t j = prefix_pick(pre, len - 1, q);
         const uint64_t excl = j ? pre[j - 1] : 0;
         const Tup r = rw[beg[j] + (q - excl)];
         const Tup sj = S[tb + j];
-        st_val(cols.r + ob + q, mat_payload(&r));
-        st_val(cols.s + ob + q, mat_payload(&sj));
-        if (cols.rkey) st_val(cols.rkey + ob + q, (MatVal)tup_key(r));
-        if (cols.skey) st_val(cols.skey + ob + q, (MatVal)tup_key(sj));
+        st_col(cols.r + ob + q, mat_payload(&r));
+        st_col(cols.s + ob + q, mat_payload(&sj));
+        if (cols.rkey) st_col(cols.rkey + ob + q, (MatVal)tup_key(r));
+        if (cols.skey) st_col(cols.skey + ob + q, (MatVal)tup_key(sj));
     }
 }
 
-struct BandTab {
-    uint64_t ntiles;
-    uint64_t *cnt, *base, *ibase, *bounds, *tot;
-};
-
 // the bounds and count passes; ent null: no entries are kept
-static BandTab band_count_passes(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S,
+static TileTab band_count_passes(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S,
                                  uint64_t nS, int64_t lo, int64_t hi, uint2* ent,
                                  hipStream_t st) {
-    BandTab b;
-    b.ntiles = (nS + MT_TILE - 1) / MT_TILE;
-    uint64_t* tab = (uint64_t*)ws->scratch("band_tab", (5 * b.ntiles + 2) * 8);
-    b.cnt = tab;
-    b.base = tab + b.ntiles;
-    b.ibase = tab + 2 * b.ntiles;
-    b.bounds = tab + 3 * b.ntiles;  // 2 per tile
-    b.tot = tab + 5 * b.ntiles;
-    {
-        TraceScope ts(ws, "k_band_bounds", st);
-        hipLaunchKernelGGL(k_band_bounds, dim3((uint32_t)((b.ntiles + 255) / 256)), dim3(256),
-                           0, st, R, nR, S, nS, lo, hi, b.ntiles, b.bounds);
-        SMJ_CHECK(hipGetLastError());
-    }
+    const TileTab b = tile_tab(ws, "band_tab", (nS + MT_TILE - 1) / MT_TILE, 2);
+    launch_tile_bounds(ws, "k_band_bounds", k_band_bounds, b.ntiles, st, R, nR, S, nS, lo, hi,
+                       b.ntiles, b.bounds);
     {
         TraceScope ts(ws, "k_band_count", st);
         hipLaunchKernelGGL(k_band_count, dim3((uint32_t)b.ntiles), dim3(MT_THREADS), 0, st, R,
@@ -287,36 +226,25 @@ uint64_t band_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint6
                    void* s_key_out, uint64_t out_cap, hipStream_t st) {
     if (lo > hi || nR == 0 || nS == 0) return 0;
     uint2* ent = out_cap ? (uint2*)ws->scratch("band_ent", nS * sizeof(uint2)) : nullptr;
-    const BandTab b = band_count_passes(ws, R, nR, S, nS, lo, hi, ent, st);
-    mat_scan(ws, b.cnt, b.ntiles, b.base, b.ibase, b.tot, st);
-    uint64_t* h = (uint64_t*)ws->host_pinned("band_tot_h", 16);
-    SMJ_CHECK(hipMemcpyAsync(h, b.tot, 16, hipMemcpyDeviceToHost, st));
-    SMJ_CHECK(hipStreamSynchronize(st));
-    const uint64_t total = h[0], items = h[1];
-    // work items run in output order and every tile's items but its last
-    // hold kMatPiece outputs: those below out_cap number at most one per tile
-    // plus out_cap / kMatPiece
-    const uint64_t need = b.ntiles + out_cap / kMatPiece + 1;
-    const uint64_t launch = items < need ? items : need;
-    if (launch && out_cap) {
+    const TileTab b = band_count_passes(ws, R, nR, S, nS, lo, hi, ent, st);
+    const MatFinish f = mat_finish(ws, "band_tot_h", b, out_cap, st);
+    if (f.launch) {
         const BandCols cols{(MatVal*)r_out, (MatVal*)s_out, (MatVal*)r_key_out,
                             (MatVal*)s_key_out};
         TraceScope ts(ws, "k_band_write", st);
-        hipLaunchKernelGGL(k_band_write, dim3((uint32_t)launch), dim3(MT_THREADS), 0, st, R, S,
+        hipLaunchKernelGGL(k_band_write, dim3((uint32_t)f.launch), dim3(MT_THREADS), 0, st, R, S,
                            nS, lo, hi, b.bounds, ent, b.cnt, b.base, b.ibase, b.ntiles, out_cap,
                            cols);
         SMJ_CHECK(hipGetLastError());
     }
-    return total;
+    return f.total;
 }
 
 void band_join_count(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
                      int64_t lo, int64_t hi, unsigned long long* count_dev, hipStream_t st) {
     if (lo > hi || nR == 0 || nS == 0) return;
-    const BandTab b = band_count_passes(ws, R, nR, S, nS, lo, hi, nullptr, st);
-    hipLaunchKernelGGL(k_band_total, dim3((uint32_t)((b.ntiles + BT_BLOCK - 1) / BT_BLOCK)),
-                       dim3(BT_BLOCK), 0, st, b.cnt, b.ntiles, count_dev);
-    SMJ_CHECK(hipGetLastError());
+    const TileTab b = band_count_passes(ws, R, nR, S, nS, lo, hi, nullptr, st);
+    tile_total(ws, nullptr, b.cnt, b.ntiles, count_dev, st);
 }
 
 }  // namespace smj

@@ -206,12 +206,4 @@ __device__ __forceinline__ GCarry gc_block_scan(GCarry v, GCarry* wl, GCarry* to
     return gc_comb(p, v);
 }
 
-__device__ __forceinline__ void st_i64(int64_t* p, int64_t v) {
-#if SMJ_NT_STORES
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-
 }  // namespace smj

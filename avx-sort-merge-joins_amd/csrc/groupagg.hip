@@ -239,56 +239,35 @@ k_group_write(const Tup* __restrict__ in, uint64_t n, uint32_t gsh,
         if (cols.key) {
             int64_t k = key[j];
             if (gsh != 0 && s < gi) k = ga_key(in + s);  // s <= gi < n
-            st_val(cols.key + r, (MatVal)k);
+            st_col(cols.key + r, (MatVal)k);
         }
-        if (cols.start) st_i64(cols.start + r, (int64_t)s);
-        if (cols.count) st_i64(cols.count + r, (int64_t)(gi - s + 1));
+        if (cols.start) st_col(cols.start + r, (int64_t)s);
+        if (cols.count) st_col(cols.count + r, (int64_t)(gi - s + 1));
         if (AGG) {
             const GAgg a = far ? ga_comb(ia, x[j]) : x[j];
-            if (cols.sum) st_i64(cols.sum + r, a.sum);
-            if (AGG == 2 && cols.mn) st_val(cols.mn + r, a.mn);
-            if (AGG == 2 && cols.mx) st_val(cols.mx + r, a.mx);
+            if (cols.sum) st_col(cols.sum + r, a.sum);
+            if (AGG == 2 && cols.mn) st_col(cols.mn + r, a.mn);
+            if (AGG == 2 && cols.mx) st_col(cols.mx + r, a.mx);
         }
     }
 }
 
-// the tiles' heads added to *total, one atomic per 1024 tiles (k_band_total's
-// reduction)
-constexpr uint32_t GT_BLOCK = 1024;
-
-__global__ void __launch_bounds__(GT_BLOCK)
-k_group_total(const uint64_t* __restrict__ cnt, uint64_t ntiles, unsigned long long* total) {
-    __shared__ uint64_t ws[GT_BLOCK / 64];
-    const uint64_t t = (uint64_t)blockIdx.x * GT_BLOCK + threadIdx.x;
-    const uint64_t c = wave_sum(t < ntiles ? cnt[t] : 0);
-    if (lane_id() == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t a = 0;
-        for (uint32_t w = 0; w < GT_BLOCK / 64; w++) a += ws[w];
-        if (a) atomicAdd(total, (unsigned long long)a);
-    }
-}
-
-struct GroupTab {
-    uint64_t ntiles;
+// materialize.hip's tile table with 0 bounds words (`bounds` is unused and
+// equals `tot`) and, in tile_tab's extra bytes behind tot[0..1], the carry
+// step's tables
+struct GroupTab : TileTab {
     uint32_t nb;  // workgroups of the carry step
-    uint64_t *cnt, *base, *ibase, *tot;
     GCarry *tail, *carry, *part, *pexcl;
 };
 
 static GroupTab group_tab(Workspace* ws, uint64_t n) {
     GroupTab g;
-    g.ntiles = (n + GA_TILE - 1) / GA_TILE;
-    g.nb = (uint32_t)((g.ntiles + GC_BLOCK - 1) / GC_BLOCK);
-    const size_t words = 3 * g.ntiles + 2 + ((3 * g.ntiles) & 1);  // the GCarry tables 16-aligned
-    char* tab = (char*)ws->scratch(
-        "group_tab", words * 8 + (2 * g.ntiles + 2 * (size_t)g.nb) * sizeof(GCarry));
-    g.cnt = (uint64_t*)tab;
-    g.base = g.cnt + g.ntiles;
-    g.ibase = g.base + g.ntiles;
-    g.tot = g.ibase + g.ntiles;
-    g.tail = (GCarry*)(tab + words * 8);
+    const uint64_t ntiles = (n + GA_TILE - 1) / GA_TILE;
+    g.nb = (uint32_t)((ntiles + GC_BLOCK - 1) / GC_BLOCK);
+    const size_t pad = ((3 * ntiles) & 1) * 8;  // the GCarry tables 16-aligned
+    static_cast<TileTab&>(g) = tile_tab(
+        ws, "group_tab", ntiles, 0, pad + (2 * ntiles + 2 * (size_t)g.nb) * sizeof(GCarry));
+    g.tail = (GCarry*)((char*)(g.tot + 2) + pad);
     g.carry = g.tail + g.ntiles;
     g.part = g.carry + g.ntiles;
     g.pexcl = g.part + g.nb;
@@ -357,10 +336,7 @@ void group_count(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift,
     if (n == 0) return;
     const GroupTab g = group_tab(ws, n);
     group_count_pass<0>(ws, in, n, group_shift, g, false, st);
-    TraceScope ts(ws, "k_group_total", st);
-    hipLaunchKernelGGL(k_group_total, dim3((uint32_t)((g.ntiles + GT_BLOCK - 1) / GT_BLOCK)),
-                       dim3(GT_BLOCK), 0, st, g.cnt, g.ntiles, groups_dev);
-    SMJ_CHECK(hipGetLastError());
+    tile_total(ws, "k_group_total", g.cnt, g.ntiles, groups_dev, st);
 }
 
 }  // namespace smj

@@ -52,9 +52,9 @@ struct PairCols {
 
 __device__ __forceinline__ void st_pair(const PairCols& o, uint64_t q, MatVal rpay,
                                         const Tup& s) {
-    st_val(o.r + q, rpay);
-    st_val(o.s + q, mat_payload(&s));
-    if (o.key) st_val(o.key + q, (MatVal)tup_key(s));
+    st_col(o.r + q, rpay);
+    st_col(o.s + q, mat_payload(&s));
+    if (o.key) st_col(o.key + q, (MatVal)tup_key(s));
 }
 
 // per tile: R window [lo, hi), S start of the first key run, S end of the last
@@ -62,19 +62,7 @@ __global__ void __launch_bounds__(256)
 k_mat_bounds(const Tup* __restrict__ R, uint64_t nR, const Tup* __restrict__ S,
              uint64_t nS, uint64_t ntiles, uint64_t* __restrict__ bounds) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ntiles) return;
-    const uint64_t tb = t * MT_TILE;
-    const uint64_t te = min(tb + MT_TILE, nS);
-    const TupKey rk{R}, sk{S};
-    const int64_t kf = sk(tb), kl = sk(te - 1);
-    const uint64_t rlo = key_search<false>(rk, 0, nR, kf);
-    const uint64_t rhi = key_search<true>(rk, rlo, nR, kl);
-    const uint64_t s0 = (tb > 0 && sk(tb - 1) == kf) ? key_search<false>(sk, 0, tb, kf) : tb;
-    const uint64_t se = (te < nS && sk(te) == kl) ? key_search<true>(sk, te, nS, kl) : te;
-    bounds[4 * t + 0] = rlo;
-    bounds[4 * t + 1] = rhi;
-    bounds[4 * t + 2] = s0;
-    bounds[4 * t + 3] = se;
+    if (t < ntiles) tile_bounds(R, nR, S, nS, t).put(bounds + 4 * t);
 }
 
 struct MatLDS {
@@ -85,82 +73,24 @@ struct MatLDS {
     int64_t rkey[MT_RWIN];   // the R window's keys, when it fits
     uint64_t ends[4];
     uint64_t wsum[MT_THREADS / 64 + 1];
-    static constexpr bool kRlo = false;
+    __device__ __forceinline__ void put_run(uint32_t u, uint64_t, uint64_t rlo, uint64_t rhi,
+                                            uint32_t a, uint32_t e) {
+        rc[u] = rhi - rlo;
+        s0[u] = (uint16_t)a;
+        se[u] = (uint16_t)e;
+    }
 };
 
 // the pair mode also keeps where the element's R run starts, as an offset
 // into the tile's R window: 22 KB, 7 workgroups per CU
 struct MatLDSPairs : MatLDS {
     uint64_t rlo[MT_TILE];
-    static constexpr bool kRlo = true;
+    __device__ __forceinline__ void put_run(uint32_t u, uint64_t Rlo, uint64_t lo, uint64_t hi,
+                                            uint32_t a, uint32_t e) {
+        MatLDS::put_run(u, Rlo, lo, hi, a, e);
+        rlo[u] = lo;
+    }
 };
-
-template <class K, class LDS>
-__device__ __forceinline__ void mat_runs(K rkey, uint64_t Rlo, uint64_t Rhi,
-                                         uint32_t i0, uint32_t i1, uint32_t len,
-                                         LDS& L) {
-    // run start of the thread's first element, run end of its last (LDS)
-    uint32_t a = 0, b = i0;
-    {
-        const int64_t k = L.key[i0];
-        while (a < b) {
-            const uint32_t m = (a + b) >> 1;
-            if (L.key[m] < k) a = m + 1; else b = m;
-        }
-    }
-    uint32_t c = i1, d = len;
-    {
-        const int64_t k = L.key[i1 - 1];
-        while (c < d) {
-            const uint32_t m = (c + d) >> 1;
-            if (L.key[m] <= k) c = m + 1; else d = m;
-        }
-    }
-    uint32_t s0 = a;
-    uint64_t rlo, rhi = Rlo;
-    uint32_t i = i0;
-    while (i < i1) {
-        const int64_t k = L.key[i];
-        uint32_t j = i + 1;
-        while (j < i1 && L.key[j] == k) j++;
-        if (i != i0) s0 = i;
-        rlo = key_gallop<false>(rkey, rhi, Rhi, k);
-        rhi = key_gallop<true>(rkey, rlo, Rhi, k);
-        const uint32_t e = j < i1 ? j : c;
-        for (uint32_t u = i; u < j; u++) {
-            L.rc[u] = rhi - rlo;
-            L.s0[u] = (uint16_t)s0;
-            L.se[u] = (uint16_t)e;
-            if constexpr (LDS::kRlo) L.rlo[u] = rlo - Rlo;
-        }
-        i = j;
-    }
-}
-
-// key runs and R match counts of S[tb, tb + len)
-template <class LDS>
-__device__ void mat_tile(const Tup* __restrict__ R, const Tup* __restrict__ S,
-                         const uint64_t* __restrict__ bounds, uint64_t t,
-                         uint64_t tb, uint32_t len, LDS& L) {
-    const uint32_t tid = threadIdx.x;
-    if (tid < 4) L.ends[tid] = bounds[4 * t + tid];
-    for (uint32_t i = tid; i < len; i += MT_THREADS) L.key[i] = tup_key(S[tb + i]);
-    __syncthreads();
-    const uint64_t Rlo = L.ends[0], Rhi = L.ends[1];
-    const bool staged = Rhi - Rlo <= MT_RWIN;
-    if (staged)
-        for (uint32_t i = tid; i < Rhi - Rlo; i += MT_THREADS) L.rkey[i] = tup_key(R[Rlo + i]);
-    __syncthreads();
-    const uint32_t i0 = tid * MT_IPT;
-    if (i0 >= len) return;
-    const uint32_t i1 = min(i0 + (uint32_t)MT_IPT, len);
-    if (staged) {
-        const int64_t* rk = L.rkey;
-        mat_runs([rk](uint64_t i) { return rk[i]; }, 0, Rhi - Rlo, i0, i1, len, L);
-    } else {
-        mat_runs(TupKey{R}, Rlo, Rhi, i0, i1, len, L);
-    }
-}
 
 // MODE pairs: a bitmap tile also leaves partner[S index] = the offset of the
 // element's partner in the tile's R window (partner null: a count-only call,
@@ -177,7 +107,8 @@ k_mat_count(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
     __shared__ LDS L;
     const uint64_t tb = (uint64_t)blockIdx.x * MT_TILE;
     const uint32_t len = (uint32_t)min((uint64_t)MT_TILE, nS - tb);
-    mat_tile(R, S, bounds, blockIdx.x, tb, len, L);
+    // key runs and R match counts of the tile
+    run_tile<4>(R, S, bounds, blockIdx.x, tb, len, L, L.rkey);
     if constexpr (MODE == MAT_SEMI) {
         __syncthreads();
         uint32_t kept = 0;  // of the wave's elements
@@ -188,14 +119,8 @@ k_mat_count(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
             if (lane_id() == 0) bitmap[blockIdx.x * (MT_TILE / 64) + e / 64] = bal;
             kept += __popcll(bal);
         }
-        if (lane_id() == 0) L.wsum[threadIdx.x >> 6] = kept;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t t = 0;
-            for (int w = 0; w < MT_THREADS / 64; w++) t += L.wsum[w];
-            tile_out[blockIdx.x] = t;
-            multi_out[blockIdx.x] = 0;
-        }
+        if (threadIdx.x == 0) multi_out[blockIdx.x] = 0;
+        tile_sum_store(kept, L.wsum, tile_out);
         return;
     }
     uint64_t s = 0;
@@ -221,14 +146,7 @@ k_mat_count(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
         }
     }
     if (threadIdx.x == 0) multi_out[blockIdx.x] = (uint32_t)multi;
-    s = wave_sum(s);
-    if (lane_id() == 0) L.wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t t = 0;
-        for (int w = 0; w < MT_THREADS / 64; w++) t += L.wsum[w];
-        tile_out[blockIdx.x] = t;
-    }
+    tile_reduce_store(s, L.wsum, tile_out);
 }
 
 __device__ __forceinline__ uint64_t mat_items(uint64_t c) {
@@ -310,6 +228,65 @@ void mat_scan(Workspace* ws, const uint64_t* cnt, uint64_t ntiles, uint64_t* bas
     SMJ_CHECK(hipGetLastError());
 }
 
+TileTab tile_tab(Workspace* ws, const char* scratch_name, uint64_t ntiles,
+                 uint32_t bounds_words, size_t extra_bytes) {
+    TileTab b;
+    b.ntiles = ntiles;
+    b.cnt = (uint64_t*)ws->scratch(scratch_name,
+                                   ((3 + bounds_words) * ntiles + 2) * 8 + extra_bytes);
+    b.base = b.cnt + ntiles;
+    b.ibase = b.cnt + 2 * ntiles;
+    b.bounds = b.cnt + 3 * ntiles;
+    b.tot = b.cnt + (3 + bounds_words) * ntiles;
+    return b;
+}
+
+MatFinish mat_finish(Workspace* ws, const char* pinned_name, const TileTab& b, uint64_t out_cap,
+                     hipStream_t st) {
+    mat_scan(ws, b.cnt, b.ntiles, b.base, b.ibase, b.tot, st);
+    uint64_t* h = (uint64_t*)ws->host_pinned(pinned_name, 16);
+    SMJ_CHECK(hipMemcpyAsync(h, b.tot, 16, hipMemcpyDeviceToHost, st));
+    SMJ_CHECK(hipStreamSynchronize(st));
+    const uint64_t total = h[0], items = h[1];
+    // work items run in output order and every tile's items but its last
+    // hold kMatPiece outputs: the items below out_cap number at most one per
+    // tile plus out_cap / kMatPiece (a small buffer for a huge skewed join
+    // launches no more than that)
+    const uint64_t need = b.ntiles + out_cap / kMatPiece + 1;
+    return MatFinish{total, out_cap ? (items < need ? items : need) : 0};
+}
+
+// the count forms: the tile counts added to *total, one atomic per 1024 tiles
+constexpr uint32_t TT_BLOCK = 1024;
+
+template <class C>
+__global__ void __launch_bounds__(TT_BLOCK)
+k_tile_total(const C* __restrict__ cnt, uint64_t ntiles, unsigned long long* total) {
+    __shared__ uint64_t ws[TT_BLOCK / 64];
+    const uint64_t t = (uint64_t)blockIdx.x * TT_BLOCK + threadIdx.x;
+    const uint64_t c = wave_sum((uint64_t)(t < ntiles ? cnt[t] : 0));
+    if (lane_id() == 0) ws[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t a = 0;
+        for (uint32_t w = 0; w < TT_BLOCK / 64; w++) a += ws[w];
+        if (a) atomicAdd(total, (unsigned long long)a);
+    }
+}
+
+template <class C>
+void tile_total(Workspace* ws, const char* trace_name, const C* cnt, uint64_t ntiles,
+                unsigned long long* total_dev, hipStream_t st) {
+    TraceScope ts(trace_name ? ws : nullptr, trace_name, st);
+    hipLaunchKernelGGL(k_tile_total<C>, dim3((uint32_t)((ntiles + TT_BLOCK - 1) / TT_BLOCK)),
+                       dim3(TT_BLOCK), 0, st, cnt, ntiles, total_dev);
+    SMJ_CHECK(hipGetLastError());
+}
+template void tile_total(Workspace*, const char*, const uint64_t*, uint64_t,
+                         unsigned long long*, hipStream_t);
+template void tile_total(Workspace*, const char*, const uint32_t*, uint64_t,
+                         unsigned long long*, hipStream_t);
+
 // MODE tuples writes `out`; MODE pairs writes the columns `cols` (semi joins
 // run MODE tuples: all their tiles are bitmap tiles)
 template <int MODE>
@@ -323,24 +300,10 @@ k_mat_write(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
     using LDS = std::conditional_t<MODE == MAT_PAIRS, MatLDSPairs, MatLDS>;
     __shared__ LDS L;
     __shared__ uint64_t sh_t;
-    const uint64_t w = blockIdx.x;
-    if (threadIdx.x == 0) {
-        // the last tile whose first item is <= w owns item w
-        uint64_t lo = 0, hi = ntiles;
-        while (lo < hi) {
-            const uint64_t m = (lo + hi) >> 1;
-            if (ibase[m] <= w) lo = m + 1; else hi = m;
-        }
-        sh_t = lo - 1;
-    }
-    __syncthreads();
-    const uint64_t t = sh_t;
-    const uint64_t q0 = (w - ibase[t]) * kMatPiece;
-    const uint64_t q1 = min(q0 + kMatPiece, cnt[t]);
-    const uint64_t ob = base[t];
-    if (ob + q0 >= out_cap) return;  // uniform over the workgroup
-    const uint64_t tb = t * MT_TILE;
-    const uint32_t len = (uint32_t)min((uint64_t)MT_TILE, nS - tb);
+    const MatPiece pc = mat_piece(ibase, cnt, base, ntiles, nS, out_cap, &sh_t);
+    if (!pc.live) return;
+    const uint64_t t = pc.t, q0 = pc.q0, q1 = pc.q1, ob = pc.ob, tb = pc.tb;
+    const uint32_t len = pc.len;
     if (!multi[t]) {
         // key join tile (one piece): copy the matching elements in order
         constexpr uint32_t NW = MT_TILE / 64;
@@ -374,7 +337,7 @@ k_mat_write(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
         }
         return;
     }
-    mat_tile(R, S, bounds, t, tb, len, L);
+    run_tile<4>(R, S, bounds, t, tb, len, L, L.rkey);
     // inclusive prefix of the counts over the tile
     const uint32_t i0 = threadIdx.x * MT_IPT;
     const uint32_t i1 = min(i0 + (uint32_t)MT_IPT, len);
@@ -389,28 +352,22 @@ k_mat_write(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
     const int64_t first_s0 = (int64_t)L.ends[2], last_se = (int64_t)L.ends[3];
     for (uint64_t q = q0 + threadIdx.x; q < q1; q += MT_THREADS) {
         if (ob + q >= out_cap) break;
-        // element j: the first inclusive prefix above q
-        uint32_t lo = 0, hi = len - 1;
-        while (lo < hi) {
-            const uint32_t m = (lo + hi) >> 1;
-            if (L.rc[m] <= q) lo = m + 1; else hi = m;
-        }
-        const uint32_t j = lo;
+        // element j: the first inclusive prefix above q (q < cnt[t] = rc[len - 1])
+        const uint32_t j = prefix_pick(L.rc, len - 1, q);
         const uint64_t excl = j ? L.rc[j - 1] : 0;
         const uint64_t rcj = L.rc[j] - excl;
-        const uint32_t a = L.s0[j], c = L.se[j];
-        const int64_t s0 = a == 0 ? first_s0 : (int64_t)(tb + a);
-        const int64_t se = c == len ? last_se : (int64_t)(tb + c);
+        int64_t s0, se;
+        run_extent(L.s0, L.se, j, tb, len, first_s0, last_se, s0, se);
         const uint64_t sc = (uint64_t)(se - s0);
         // the run's output starts (tb + j - s0) * rcj outputs before element
         // j's first (mod 2^64 when the run began in an earlier tile)
         const uint64_t off = q - (excl - (uint64_t)((int64_t)(tb + j) - s0) * rcj);
         if constexpr (MODE == MAT_PAIRS) {
             // R-major: R tuple off / sc of the run, S tuple off % sc
-            uint64_t d = off;
-            if (sc != 1) d = ((off | sc) >> 32) ? off / sc : (uint32_t)off / (uint32_t)sc;
+            uint64_t d;
+            const uint64_t m = run_pair(off, sc, d);
             const Tup* r = R + L.ends[0] + L.rlo[j] + d;
-            st_pair(cols, ob + q, mat_payload(r), S[(uint64_t)s0 + (off - d * sc)]);
+            st_pair(cols, ob + q, mat_payload(r), S[(uint64_t)s0 + m]);
         } else {
             const uint64_t src = (uint64_t)s0 + (sc == 1 ? 0 : off % sc);
             st_stream(out + ob + q, S[src]);
@@ -435,45 +392,26 @@ static uint64_t mat_passes(Workspace* ws, const Tup* R, uint64_t nR, const Tup* 
     const uint64_t ntiles = (nS + MT_TILE - 1) / MT_TILE;
     uint32_t* partner = nullptr;
     if (MODE == MAT_PAIRS && out_cap) partner = (uint32_t*)ws->scratch("mat_partner", nS * 4);
-    uint64_t* tab = (uint64_t*)ws->scratch("mat_tab", (7 * ntiles + 2) * 8);
+    const TileTab b = tile_tab(ws, "mat_tab", ntiles, 4);
     uint64_t* bitmap = (uint64_t*)ws->scratch("mat_bits", ntiles * (MT_TILE / 8));
     uint32_t* multi = (uint32_t*)ws->scratch("mat_multi", ntiles * 4);
-    uint64_t* cnt = tab;
-    uint64_t* base = tab + ntiles;
-    uint64_t* ibase = tab + 2 * ntiles;
-    uint64_t* bounds = tab + 3 * ntiles;  // 4 per tile
-    uint64_t* tot = tab + 7 * ntiles;
-    {
-        TraceScope ts(ws, "k_mat_bounds", st);
-        hipLaunchKernelGGL(k_mat_bounds, dim3((uint32_t)((ntiles + 255) / 256)), dim3(256),
-                           0, st, R, nR, S, nS, ntiles, bounds);
-        SMJ_CHECK(hipGetLastError());
-    }
+    launch_tile_bounds(ws, "k_mat_bounds", k_mat_bounds, ntiles, st, R, nR, S, nS, ntiles,
+                       b.bounds);
     {
         TraceScope ts(ws, count_name, st);
         hipLaunchKernelGGL(k_mat_count<MODE>, dim3((uint32_t)ntiles), dim3(MT_THREADS), 0,
-                           st, R, S, nS, bounds, cnt, bitmap, multi, partner, anti);
+                           st, R, S, nS, b.bounds, b.cnt, bitmap, multi, partner, anti);
         SMJ_CHECK(hipGetLastError());
     }
-    mat_scan(ws, cnt, ntiles, base, ibase, tot, st);
-    uint64_t* h = (uint64_t*)ws->host_pinned("mat_tot_h", 16);
-    SMJ_CHECK(hipMemcpyAsync(h, tot, 16, hipMemcpyDeviceToHost, st));
-    SMJ_CHECK(hipStreamSynchronize(st));
-    const uint64_t total = h[0], items = h[1];
-    // work items run in output order and every tile's items but its last
-    // hold kMatPiece outputs: the items below out_cap number at most one per
-    // tile plus out_cap / kMatPiece (a small buffer for a huge skewed join
-    // launches no more than that)
-    const uint64_t need = ntiles + out_cap / kMatPiece + 1;
-    const uint64_t launch = items < need ? items : need;
-    if (launch && out_cap) {
+    const MatFinish f = mat_finish(ws, "mat_tot_h", b, out_cap, st);
+    if (f.launch) {
         TraceScope ts(ws, write_name, st);
-        hipLaunchKernelGGL(k_mat_write<WMODE>, dim3((uint32_t)launch), dim3(MT_THREADS), 0,
-                           st, R, S, nS, bounds, cnt, base, ibase, ntiles, bitmap, multi,
+        hipLaunchKernelGGL(k_mat_write<WMODE>, dim3((uint32_t)f.launch), dim3(MT_THREADS), 0,
+                           st, R, S, nS, b.bounds, b.cnt, b.base, b.ibase, ntiles, bitmap, multi,
                            out, out_cap, partner, cols);
         SMJ_CHECK(hipGetLastError());
     }
-    return total;
+    return f.total;
 }
 
 uint64_t materialize(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S,

@@ -53,15 +53,6 @@ struct OuterCols {
     MatVal* key;
 };
 
-template <class T>
-__device__ __forceinline__ void st_col(T* p, T v) {
-#if SMJ_NT_STORES
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-
 // row q: R tuple r and S tuple s, -1 for an absent side (never both)
 __device__ __forceinline__ void st_outer(const OuterCols& o, uint64_t q,
                                          const Tup* __restrict__ R,
@@ -93,25 +84,15 @@ k_outer_bounds(const Tup* __restrict__ R, uint64_t nR, const Tup* __restrict__ S
                uint64_t nS, uint64_t ntiles, uint64_t* __restrict__ bounds) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ntiles) return;
-    const uint64_t tb = t * MT_TILE;
-    const uint64_t te = min(tb + MT_TILE, nS);
+    const TileBounds x = tile_bounds(R, nR, S, nS, t);
     const TupKey rk{R}, sk{S};
-    const int64_t kf = sk(tb), kl = sk(te - 1);
-    const uint64_t rlo = key_search<false>(rk, 0, nR, kf);
-    const uint64_t rhi = key_search<true>(rk, rlo, nR, kl);
-    const bool cont = tb > 0 && sk(tb - 1) == kf;  // the first run began earlier
-    const uint64_t s0 = cont ? key_search<false>(sk, 0, tb, kf) : tb;
-    const uint64_t se = (te < nS && sk(te) == kl) ? key_search<true>(sk, te, nS, kl) : te;
     uint64_t os = 0;
-    if (cont) os = key_search<true>(rk, rlo, rhi, kf);
-    else if (tb > 0) os = key_search<true>(rk, 0, rlo, sk(tb - 1));
+    if (x.cont) os = key_search<true>(rk, x.rlo, x.rhi, x.kf);
+    else if (x.tb > 0) os = key_search<true>(rk, 0, x.rlo, sk(x.tb - 1));
     uint64_t* b = bounds + OB_WORDS * t;
-    b[0] = rlo;
-    b[1] = rhi;
-    b[2] = s0;
-    b[3] = se;
+    x.put(b);
     b[4] = os;
-    b[5] = te == nS ? nR : rhi;
+    b[5] = x.te == nS ? nR : x.rhi;
 }
 
 // 22.4 KB: 7 workgroups per CU.  The staged R keys are dead once the runs are
@@ -130,7 +111,9 @@ struct OuterLDS {
     uint64_t wsum[MT_THREADS / 64 + 1];
 };
 
-// mat_runs of materialize.hip, keeping both ends of the R run; rkey(i) = key
+// run_walk of mat_common.hpp, keeping both ends of the R run.  Its own copy,
+// with outer_tile below for run_tile: through the shared pair k_outer_count
+// measured 0.3 to 0.5 % slower at 8 B.  rkey(i) = key
 // i of [Rlo, Rhi), position base + i of R
 template <class K>
 __device__ __forceinline__ void outer_runs(K rkey, uint64_t Rlo, uint64_t Rhi, uint64_t base,
@@ -233,31 +216,7 @@ k_outer_count(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
         s += g + m;
     }
     if (threadIdx.x == 0) s += outer_tail(L, len, keep);
-    s = wave_sum(s);
-    if (lane_id() == 0) L.wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t t = 0;
-        for (int w = 0; w < MT_THREADS / 64; w++) t += L.wsum[w];
-        tile_out[blockIdx.x] = t;
-    }
-}
-
-// the count form: the tile sums added to *total, one atomic per 1024 tiles
-constexpr uint32_t OT_BLOCK = 1024;
-
-__global__ void __launch_bounds__(OT_BLOCK)
-k_outer_total(const uint64_t* __restrict__ cnt, uint64_t ntiles, unsigned long long* total) {
-    __shared__ uint64_t ws[OT_BLOCK / 64];
-    const uint64_t t = (uint64_t)blockIdx.x * OT_BLOCK + threadIdx.x;
-    const uint64_t c = wave_sum(t < ntiles ? cnt[t] : 0);
-    if (lane_id() == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t a = 0;
-        for (uint32_t w = 0; w < OT_BLOCK / 64; w++) a += ws[w];
-        if (a) atomicAdd(total, (unsigned long long)a);
-    }
+    tile_reduce_store(s, L.wsum, tile_out);
 }
 
 __global__ void __launch_bounds__(64)
@@ -272,24 +231,10 @@ k_outer_write(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
               uint64_t ntiles, uint64_t out_cap, OuterCols cols) {
     __shared__ OuterLDS L;
     __shared__ uint64_t sh_t;
-    const uint64_t w = blockIdx.x;
-    if (threadIdx.x == 0) {
-        // the last tile whose first item is <= w owns item w
-        uint64_t lo = 0, hi = ntiles;
-        while (lo < hi) {
-            const uint64_t m = (lo + hi) >> 1;
-            if (ibase[m] <= w) lo = m + 1; else hi = m;
-        }
-        sh_t = lo - 1;
-    }
-    __syncthreads();
-    const uint64_t t = sh_t;
-    const uint64_t q0 = (w - ibase[t]) * kMatPiece;
-    const uint64_t q1 = min(q0 + kMatPiece, cnt[t]);
-    const uint64_t ob = base[t];
-    if (ob + q0 >= out_cap) return;  // uniform over the workgroup
-    const uint64_t tb = t * MT_TILE;
-    const uint32_t len = (uint32_t)min((uint64_t)MT_TILE, nS - tb);
+    const MatPiece pc = mat_piece(ibase, cnt, base, ntiles, nS, out_cap, &sh_t);
+    if (!pc.live) return;
+    const uint64_t t = pc.t, q0 = pc.q0, q1 = pc.q1, ob = pc.ob, tb = pc.tb;
+    const uint32_t len = pc.len;
     outer_tile(R, S, bounds, t, tb, len, L);
     // inclusive prefix over gap(0), match(0), gap(1), ..., match(len - 1), tail
     const uint32_t i0 = threadIdx.x * MT_IPT;
@@ -320,12 +265,7 @@ k_outer_write(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
     for (uint64_t q = q0 + threadIdx.x; q < q1; q += MT_THREADS) {
         if (ob + q >= out_cap) break;
         // entry x: the first inclusive prefix above q (q < cnt[t] = pre[2 len])
-        uint32_t lo = 0, hi = 2 * len;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (L.u.pre[mid] <= q) lo = mid + 1; else hi = mid;
-        }
-        const uint32_t x = lo, j = x >> 1;
+        const uint32_t x = prefix_pick(L.u.pre, 2 * len, q), j = x >> 1;
         const uint64_t excl = x ? L.u.pre[x - 1] : 0;
         if (!(x & 1)) {
             // a gap ends where element j's R run starts, the tail where the
@@ -340,18 +280,16 @@ k_outer_write(const Tup* __restrict__ R, const Tup* __restrict__ S, uint64_t nS,
             st_outer(cols, ob + q, R, S, -1, (int64_t)(tb + j));
             continue;
         }
-        const uint32_t a = L.s0[j], c = L.se[j];
-        const int64_t s0 = a == 0 ? first_s0 : (int64_t)(tb + a);
-        const int64_t se = c == len ? last_se : (int64_t)(tb + c);
+        int64_t s0, se;
+        run_extent(L.s0, L.se, j, tb, len, first_s0, last_se, s0, se);
         const uint64_t sc = (uint64_t)(se - s0);
         // the run's pairs are cut into rcj per S element: element j's first
         // is pair (tb + j - s0) * rcj of the run; R-major, R tuple off / sc
         // of the run and S tuple off % sc
         const uint64_t off = (q - excl) + (uint64_t)((int64_t)(tb + j) - s0) * rcj;
-        uint64_t d = off;
-        if (sc != 1) d = ((off | sc) >> 32) ? off / sc : (uint32_t)off / (uint32_t)sc;
-        st_outer(cols, ob + q, R, S, (int64_t)(L.rlo[j] + d),
-                 (int64_t)((uint64_t)s0 + (off - d * sc)));
+        uint64_t d;
+        const uint64_t rem = run_pair(off, sc, d);
+        st_outer(cols, ob + q, R, S, (int64_t)(L.rlo[j] + d), (int64_t)((uint64_t)s0 + rem));
     }
 }
 
@@ -366,28 +304,12 @@ k_outer_side(const Tup* __restrict__ T, uint64_t n, int s_side, OuterCols cols) 
     }
 }
 
-struct OuterTab {
-    uint64_t ntiles;
-    uint64_t *cnt, *base, *ibase, *bounds, *tot;
-};
-
 // the bounds and count passes
-static OuterTab outer_count_passes(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S,
-                                   uint64_t nS, uint32_t keep, hipStream_t st) {
-    OuterTab b;
-    b.ntiles = (nS + MT_TILE - 1) / MT_TILE;
-    uint64_t* tab = (uint64_t*)ws->scratch("outer_tab", ((3 + OB_WORDS) * b.ntiles + 2) * 8);
-    b.cnt = tab;
-    b.base = tab + b.ntiles;
-    b.ibase = tab + 2 * b.ntiles;
-    b.bounds = tab + 3 * b.ntiles;
-    b.tot = tab + (3 + OB_WORDS) * b.ntiles;
-    {
-        TraceScope ts(ws, "k_outer_bounds", st);
-        hipLaunchKernelGGL(k_outer_bounds, dim3((uint32_t)((b.ntiles + 255) / 256)), dim3(256),
-                           0, st, R, nR, S, nS, b.ntiles, b.bounds);
-        SMJ_CHECK(hipGetLastError());
-    }
+static TileTab outer_count_passes(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S,
+                                  uint64_t nS, uint32_t keep, hipStream_t st) {
+    const TileTab b = tile_tab(ws, "outer_tab", (nS + MT_TILE - 1) / MT_TILE, OB_WORDS);
+    launch_tile_bounds(ws, "k_outer_bounds", k_outer_bounds, b.ntiles, st, R, nR, S, nS,
+                       b.ntiles, b.bounds);
     {
         TraceScope ts(ws, "k_outer_count", st);
         hipLaunchKernelGGL(k_outer_count, dim3((uint32_t)b.ntiles), dim3(MT_THREADS), 0, st, R,
@@ -423,24 +345,15 @@ uint64_t outer_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint
         }
         return total;
     }
-    const OuterTab b = outer_count_passes(ws, R, nR, S, nS, keep, st);
-    mat_scan(ws, b.cnt, b.ntiles, b.base, b.ibase, b.tot, st);
-    uint64_t* h = (uint64_t*)ws->host_pinned("outer_tot_h", 16);
-    SMJ_CHECK(hipMemcpyAsync(h, b.tot, 16, hipMemcpyDeviceToHost, st));
-    SMJ_CHECK(hipStreamSynchronize(st));
-    const uint64_t total = h[0], items = h[1];
-    // work items run in output order and every tile's items but its last
-    // hold kMatPiece rows: those below out_cap number at most one per tile
-    // plus out_cap / kMatPiece
-    const uint64_t need = b.ntiles + out_cap / kMatPiece + 1;
-    const uint64_t launch = items < need ? items : need;
-    if (launch && out_cap) {
+    const TileTab b = outer_count_passes(ws, R, nR, S, nS, keep, st);
+    const MatFinish f = mat_finish(ws, "outer_tot_h", b, out_cap, st);
+    if (f.launch) {
         TraceScope ts(ws, "k_outer_write", st);
-        hipLaunchKernelGGL(k_outer_write, dim3((uint32_t)launch), dim3(MT_THREADS), 0, st, R, S,
+        hipLaunchKernelGGL(k_outer_write, dim3((uint32_t)f.launch), dim3(MT_THREADS), 0, st, R, S,
                            nS, keep, b.bounds, b.cnt, b.base, b.ibase, b.ntiles, out_cap, cols);
         SMJ_CHECK(hipGetLastError());
     }
-    return total;
+    return f.total;
 }
 
 void outer_join_count(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint64_t nS,
@@ -454,10 +367,8 @@ void outer_join_count(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, ui
         }
         return;
     }
-    const OuterTab b = outer_count_passes(ws, R, nR, S, nS, keep, st);
-    hipLaunchKernelGGL(k_outer_total, dim3((uint32_t)((b.ntiles + OT_BLOCK - 1) / OT_BLOCK)),
-                       dim3(OT_BLOCK), 0, st, b.cnt, b.ntiles, count_dev);
-    SMJ_CHECK(hipGetLastError());
+    const TileTab b = outer_count_passes(ws, R, nR, S, nS, keep, st);
+    tile_total(ws, nullptr, b.cnt, b.ntiles, count_dev, st);
 }
 
 }  // namespace smj

@@ -464,6 +464,37 @@ uint64_t semi_join(Workspace* ws, const Tup* R, uint64_t nR, const Tup* S, uint6
 // both exclusive; tot[0..1] = the outputs and the work items in all.
 void mat_scan(Workspace* ws, const uint64_t* cnt, uint64_t ntiles, uint64_t* base,
               uint64_t* ibase, uint64_t* tot, hipStream_t st);
+// The per-tile tables of the count -> scan -> write operators, carved from one
+// scratch buffer of ((3 + bounds_words) ntiles + 2) * 8 + extra_bytes bytes:
+// cnt, base, ibase (ntiles each), bounds (bounds_words a tile), tot (2 words);
+// the extra bytes, an operator's own tables, lie behind tot.
+struct TileTab {
+    uint64_t ntiles;
+    uint64_t *cnt, *base, *ibase, *bounds, *tot;
+};
+TileTab tile_tab(Workspace* ws, const char* scratch_name, uint64_t ntiles,
+                 uint32_t bounds_words, size_t extra_bytes = 0);
+// mat_scan over the table, then its totals on the host (a 16-byte copy into
+// the named pinned buffer and ONE synchronisation of `st`): the outputs in
+// all and the work items the write pass has to launch for the first out_cap.
+struct MatFinish {
+    uint64_t total, launch;
+};
+MatFinish mat_finish(Workspace* ws, const char* pinned_name, const TileTab& tab,
+                     uint64_t out_cap, hipStream_t st);
+// The count forms: the tile counts cnt[0..ntiles) (uint64_t or uint32_t)
+// added to *total_dev, stream-ordered; traced when trace_name is not null.
+template <class C>
+void tile_total(Workspace* ws, const char* trace_name, const C* cnt, uint64_t ntiles,
+                unsigned long long* total_dev, hipStream_t st);
+// the bounds pass of an operator: one thread per tile, traced as `name`
+template <class Kern, class... A>
+inline void launch_tile_bounds(Workspace* ws, const char* name, Kern kern, uint64_t ntiles,
+                               hipStream_t st, A... args) {
+    TraceScope ts(ws, name, st);
+    hipLaunchKernelGGL(kern, dim3((uint32_t)((ntiles + 255) / 256)), dim3(256), 0, st, args...);
+    SMJ_CHECK(hipGetLastError());
+}
 
 // ---- bandjoin.hip : band join of sorted R and S (smj.h smj_dev_band_join)
 // Every pair with s.key + lo <= r.key <= s.key + hi, S-major, as columns of

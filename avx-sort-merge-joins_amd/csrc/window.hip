@@ -357,43 +357,41 @@ k_window_write(const Tup* __restrict__ in, uint64_t n, uint32_t gsh,
         // has earlier waves or tiles, and inc holds that head
         const bool far = so[j] == kNoOff;
         const uint64_t h = far ? inc.start : cb + so[j];
-        if (cols.group) st_i64(cols.group + gi, (int64_t)(row + hrank[j] - 1));
-        if (cols.row) st_i64(cols.row + gi, (int64_t)(gi - h));
+        if (cols.group) st_col(cols.group + gi, (int64_t)(row + hrank[j] - 1));
+        if (cols.row) st_col(cols.row + gi, (int64_t)(gi - h));
         if (RANKS) {
             const uint64_t p = ko[j] == kNoOff ? kinc.kstart : cb + ko[j];
-            if (cols.rank) st_i64(cols.rank + gi, (int64_t)(p - h));
-            if (cols.dense) st_i64(cols.dense + gi, (int64_t)((far ? kinc.dense : 0) + dn[j]));
+            if (cols.rank) st_col(cols.rank + gi, (int64_t)(p - h));
+            if (cols.dense) st_col(cols.dense + gi, (int64_t)((far ? kinc.dense : 0) + dn[j]));
         }
         if (AGG) {
             const GAgg a = far ? ga_comb(ia, x[j]) : x[j];
-            if (cols.sum) st_i64(cols.sum + gi, a.sum);
-            if (AGG == 2 && cols.mn) st_val(cols.mn + gi, a.mn);
-            if (AGG == 2 && cols.mx) st_val(cols.mx + gi, a.mx);
+            if (cols.sum) st_col(cols.sum + gi, a.sum);
+            if (AGG == 2 && cols.mn) st_col(cols.mn + gi, a.mn);
+            if (AGG == 2 && cols.mx) st_col(cols.mx + gi, a.mx);
         }
     }
 }
 
-struct WindowTab {
-    uint64_t ntiles;
+// materialize.hip's tile table with 0 bounds words (`bounds` is unused and
+// equals `tot`) and, in tile_tab's extra bytes behind tot[0..1], the carry
+// step's tables, as groupagg.hip's GroupTab
+struct WindowTab : TileTab {
     uint32_t nb;  // workgroups of the carry step
-    uint64_t *cnt, *base, *ibase, *tot;
     GCarry *tail, *carry, *part, *pexcl;
     KCarry *ktail, *kcarry, *kpart, *kpexcl;  // null without RANKS
 };
 
 static WindowTab window_tab(Workspace* ws, uint64_t n, bool ranks) {
     WindowTab g;
-    g.ntiles = (n + GA_TILE - 1) / GA_TILE;
-    g.nb = (uint32_t)((g.ntiles + GC_BLOCK - 1) / GC_BLOCK);
-    const size_t words = 3 * g.ntiles + 2 + ((3 * g.ntiles) & 1);  // the carry tables 16-aligned
-    const size_t items = 2 * g.ntiles + 2 * (size_t)g.nb;
-    char* tab = (char*)ws->scratch(
-        "window_tab", words * 8 + items * (sizeof(GCarry) + (ranks ? sizeof(KCarry) : 0)));
-    g.cnt = (uint64_t*)tab;
-    g.base = g.cnt + g.ntiles;
-    g.ibase = g.base + g.ntiles;
-    g.tot = g.ibase + g.ntiles;
-    g.tail = (GCarry*)(tab + words * 8);
+    const uint64_t ntiles = (n + GA_TILE - 1) / GA_TILE;
+    g.nb = (uint32_t)((ntiles + GC_BLOCK - 1) / GC_BLOCK);
+    const size_t pad = ((3 * ntiles) & 1) * 8;  // the carry tables 16-aligned
+    const size_t items = 2 * ntiles + 2 * (size_t)g.nb;
+    static_cast<TileTab&>(g) = tile_tab(
+        ws, "window_tab", ntiles, 0,
+        pad + items * (sizeof(GCarry) + (ranks ? sizeof(KCarry) : 0)));
+    g.tail = (GCarry*)((char*)(g.tot + 2) + pad);
     g.carry = g.tail + g.ntiles;
     g.part = g.carry + g.ntiles;
     g.pexcl = g.part + g.nb;

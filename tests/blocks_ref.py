@@ -14,13 +14,13 @@ import outer_ref
 from test_gpu_join_index import numpy_pairs, numpy_semi_mask
 from test_gpu_parity import rand_tuples
 
-TILE = 512     # S elements per tile: MT_TILE, csrc/mat_common.hpp:16
-RWIN = 1024    # R keys staged in LDS: MT_RWIN, csrc/mat_common.hpp:17
-PIECE = 8192   # output rows per work item: kMatPiece, csrc/mat_common.hpp:18
-SCAN = 1024    # tiles per scan block: MS_BLOCK, csrc/materialize.hip:241 (and BT_BLOCK,
-#                bandjoin.hip:163; AT_BLOCK, asofjoin.hip:181; OT_BLOCK, outerjoin.hip:247)
-BOUNDS = 256   # tiles per workgroup of a bounds kernel: csrc/materialize.hip:61 and :448
-#                (bandjoin.hip:65, asofjoin.hip:55, outerjoin.hip:91)
+TILE = 512     # S elements per tile: MT_TILE, csrc/mat_common.hpp:19
+RWIN = 1024    # R keys staged in LDS: MT_RWIN, csrc/mat_common.hpp:20
+PIECE = 8192   # output rows per work item: kMatPiece, csrc/mat_common.hpp:21
+SCAN = 1024    # tiles per scan block: MS_BLOCK, csrc/materialize.hip:159 (and the count
+#                forms' TT_BLOCK, materialize.hip:260)
+BOUNDS = 256   # tiles per workgroup of a bounds kernel: csrc/materialize.hip:61 (bandjoin.hip:65,
+#                asofjoin.hip:55, outerjoin.hip:82), launched by smj_internal.hpp:495
 
 # 2050 tiles in three scan blocks, the last of two tiles, the last tile of one
 # element; nine workgroups of a bounds kernel.  Three blocks, not two: the
