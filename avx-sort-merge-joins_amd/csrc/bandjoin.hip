@@ -42,17 +42,6 @@ static_assert(kBandWideBits <= 32, "the stored entries are 32-bit");
 
 __device__ __forceinline__ bool band_wide(uint64_t w) { return (w >> kBandWideBits) != 0; }
 
-// k + d clamped to int64; over = +1 / -1 when the sum lay above / below it
-__device__ __forceinline__ int64_t sat_add(int64_t k, int64_t d, int& over) {
-    int64_t r;
-    over = 0;
-    if (__builtin_add_overflow(k, d, &r)) {
-        over = d > 0 ? 1 : -1;
-        r = d > 0 ? INT64_MAX : INT64_MIN;
-    }
-    return r;
-}
-
 // the output columns (the key columns may be null)
 struct BandCols {
     MatVal* r;

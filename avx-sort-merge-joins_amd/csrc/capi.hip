@@ -1901,6 +1901,26 @@ void smj_dev_window(smj_workspace* ws, const tuple_t* sorted, uint64_t n, uint32
 
 uint32_t smj_window_tile(void) { return window_tile(); }
 
+void smj_dev_window_frame(smj_workspace* ws, const tuple_t* sorted, uint64_t n,
+                          uint32_t group_shift, uint32_t unit, int64_t lo, int64_t hi,
+                          int64_t* start_out, int64_t* count_out, int64_t* sum_out,
+                          value_t* min_out, value_t* max_out, value_t* first_out,
+                          value_t* last_out, smj_stream_t stream) {
+    check_group_shift("smj_dev_window_frame", group_shift);
+    if (unit != SMJ_FRAME_ROWS && unit != SMJ_FRAME_RANGE) {
+        fprintf(stderr, "[ERROR] smj_dev_window_frame: unit %u is neither SMJ_FRAME_ROWS nor "
+                "SMJ_FRAME_RANGE\n", unit);
+        abort();
+    }
+    window_frame((Workspace*)ws, (const Tup*)sorted, n, group_shift, unit == SMJ_FRAME_RANGE, lo,
+                 hi, start_out, count_out, sum_out, min_out, max_out, first_out, last_out,
+                 (hipStream_t)stream);
+}
+
+uint32_t smj_frame_tile(void) { return frame_tile(); }
+
+uint32_t smj_frame_block(void) { return frame_block(); }
+
 void smj_dev_join(smj_workspace* ws, const tuple_t* R, uint64_t nR,
                   const tuple_t* S, uint64_t nS, tuple_t* sortedR,
                   tuple_t* sortedS, uint32_t fanout_bits, int64_t key_min,

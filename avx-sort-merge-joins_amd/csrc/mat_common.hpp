@@ -44,6 +44,18 @@ __device__ __forceinline__ void st_col(T* p, T v) {
 #endif
 }
 
+// k + d clamped to int64; over = +1 / -1 when the sum lay above / below it
+// (the band join's and the window frames' key + lo, key + hi)
+__device__ __forceinline__ int64_t sat_add(int64_t k, int64_t d, int& over) {
+    int64_t r;
+    over = 0;
+    if (__builtin_add_overflow(k, d, &r)) {
+        over = d > 0 ? 1 : -1;
+        r = d > 0 ? INT64_MAX : INT64_MIN;
+    }
+    return r;
+}
+
 // first index of [lo, hi) whose key is >= k (UPPER: > k); K(i) = key i
 template <bool UPPER, class K>
 __device__ __forceinline__ uint64_t key_search(K key, uint64_t lo, uint64_t hi,

@@ -567,6 +567,23 @@ void window(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift, int6
             void* min_out, void* max_out, hipStream_t st);
 uint32_t window_tile();  // elements of `in` a workgroup of its kernels handles
 
+// ---- frame.hip : sliding window frames over a sorted relation (smj.h
+// smj_dev_window_frame)
+// One row per tuple, window()'s groups, the frame ROWS (positions i + lo ..
+// i + hi) or, with `range`, RANGE (keys key[i] + lo .. key[i] + hi, saturating)
+// BETWEEN lo AND hi inside the tuple's group: where the frame starts (-1:
+// empty), how many tuples it holds, the sum (int64, wrapping), minimum and
+// maximum of their payloads and the payloads of its first and last tuple (0
+// for an empty frame), as columns of int64 / the ABI's value_t (each may be
+// null).  Every non-null column gets n rows.  Stream-ordered, no
+// synchronisation; n == 0 or no column launches nothing.
+void window_frame(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift, bool range,
+                  int64_t lo, int64_t hi, int64_t* start_out, int64_t* count_out,
+                  int64_t* sum_out, void* min_out, void* max_out, void* first_out,
+                  void* last_out, hipStream_t st);
+uint32_t frame_tile();   // elements of `in` a workgroup of its tile kernels handles
+uint32_t frame_block();  // the inner aligned block of its range minimum and maximum
+
 // ---- datagen.hip
 void gen_pk(Tup* out, uint64_t n, uint64_t first, uint64_t total,
             uint64_t seed, hipStream_t st);

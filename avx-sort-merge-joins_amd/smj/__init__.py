@@ -76,6 +76,7 @@ DEVICE_SYMBOLS = [
     "smj_dev_outer_join", "smj_dev_outer_join_count",
     "smj_dev_group_aggregate", "smj_dev_group_count", "smj_group_tile",
     "smj_dev_window", "smj_window_tile",
+    "smj_dev_window_frame", "smj_frame_tile", "smj_frame_block",
     "smj_workspace_skew_stats", "smj_workspace_force_ballot_ranks",
     "smj_workspace_last_scatter", "smj_workspace_merge_stats",
 ]
@@ -84,6 +85,8 @@ ASOF_DIRECTIONS = {"backward": 0, "forward": 1, "nearest": 2}
 ASOF_STRICT = 4
 # smj_dev_outer_join's keep (SMJ_OUTER_KEEP_* in smj.h): left preserves R, right S
 OUTER_KEEP = {"inner": 0, "left": 1, "right": 2, "full": 3}
+# smj_dev_window_frame's unit (SMJ_FRAME_* in smj.h)
+FRAME_UNITS = {"rows": 0, "range": 1}
 
 
 def lib_path(width: int) -> str:
@@ -315,6 +318,10 @@ class Library:
             "smj_group_tile": (_U32, []),
             "smj_dev_window": (None, [_P, _P, _U64, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
             "smj_window_tile": (_U32, []),
+            "smj_dev_window_frame": (None, [_P, _P, _U64, _U32, _U32, _I64, _I64, _P, _P, _P,
+                                            _P, _P, _P, _P, _P]),
+            "smj_frame_tile": (_U32, []),
+            "smj_frame_block": (_U32, []),
             "smj_selfcheck_lds_order": (_U64, [_P, _P]),
             "smj_context_workspace": (_P, []),
             "smj_dev_gen_nonunique": (None, [_P, _P, _U64, _U64, _U64, _I64, _U32, _U64, _P]),
@@ -1134,6 +1141,68 @@ class Library:
         if n:
             self.dev_sort(T, sT)
             self.dev_window(sT, group_shift, *cols)
+        return (sT, *cols)
+
+    @staticmethod
+    def _frame(unit, lo, hi):
+        """(unit, lo, hi) of smj_dev_window_frame, checked here: the library
+        aborts on a unit it does not take.  None is unbounded."""
+        if unit not in FRAME_UNITS:
+            raise ValueError(f"unit is one of {sorted(FRAME_UNITS)}, not {unit!r}")
+        lo = -(1 << 63) if lo is None else int(lo)
+        hi = (1 << 63) - 1 if hi is None else int(hi)
+        for v in (lo, hi):
+            assert -(1 << 63) <= v < (1 << 63), "lo and hi are int64 (None: unbounded)"
+        return FRAME_UNITS[unit], lo, hi
+
+    def dev_window_frame(self, sorted, group_shift=0, unit="rows", lo=None, hi=0, start=None,
+                         count=None, sum=None, min=None, max=None, first=None, last=None):
+        """Sliding window frames (smj_dev_window_frame): one row per tuple of
+        `sorted`, PARTITION BY (key >> group_shift) ORDER BY key, the frame
+        unit "rows" (positions i + lo .. i + hi) or "range" (keys key + lo ..
+        key + hi, saturating) inside the tuple's group; lo / hi None:
+        unbounded.  Each column given gets len(sorted) rows: start (the
+        frame's first position, -1 when it is empty), count (its tuples) and
+        sum (of their payloads, wrapping) in int64, min / max (of those
+        payloads) and first / last (the payloads at its ends) in the payload
+        dtype, all 0 for an empty frame.  LAG(k) is `first` with rows lo = hi
+        = -k, LEAD(k) with lo = hi = k.  Stream-ordered: no synchronisation."""
+        gsh = self._group_shift(group_shift)
+        u, lo, hi = self._frame(unit, lo, hi)
+        n = sorted.shape[0]
+        cols = [(start, "start", torch.int64), (count, "count", torch.int64),
+                (sum, "sum", torch.int64), (min, "min", None), (max, "max", None),
+                (first, "first", None), (last, "last", None)]
+        for t, what, dt in cols:
+            if t is not None:
+                assert self._group_column(t, what, dt).shape[0] == n, what
+        ptrs = [t.data_ptr() if t is not None and n else None for t, _, _ in cols]
+        self.lib.smj_dev_window_frame(self.ws, sorted.data_ptr(), n, gsh, u, lo, hi, *ptrs,
+                                      self.stream_ptr())
+
+    def frame_tile(self):
+        """Elements one workgroup of the frame kernels handles (a host call)."""
+        return int(self.lib.smj_frame_tile())
+
+    def frame_block(self):
+        """The inner aligned block of the frame kernels' range minimum and
+        maximum (a host call); it divides frame_tile()."""
+        return int(self.lib.smj_frame_block())
+
+    def rolling(self, T, group_shift=0, unit="rows", lo=None, hi=0):
+        """The window frames of an unsorted device relation in one call: sorts
+        it (dev_sort) into a temporary and returns (sorted, start, count, sum,
+        min, max, first, last), exactly sized, on the current stream; row i of
+        every column belongs to sorted[i]."""
+        self._frame(unit, lo, hi)
+        dt = torch.int32 if self.width == 8 else torch.int64
+        n = T.shape[0]
+        sT = self.empty(n, device=T.device)
+        cols = [torch.empty(n, dtype=d, device=T.device)
+                for d in (torch.int64,) * 3 + (dt,) * 4]
+        if n:
+            self.dev_sort(T, sT)
+            self.dev_window_frame(sT, group_shift, unit, lo, hi, *cols)
         return (sT, *cols)
 
     def dev_join(self, R, S, sortedR, sortedS, count, fanout_bits=10,

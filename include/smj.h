@@ -943,6 +943,81 @@ void smj_dev_window(smj_workspace * ws, const tuple_t * sorted, uint64_t n,
  * tests; a host call, no device needed). */
 uint32_t smj_window_tile(void);
 
+/* Sliding window frames over a sorted relation: one output row per tuple, the
+ * SQL window aggregates over PARTITION BY key >> group_shift ORDER BY key with
+ * the frame ROWS or RANGE BETWEEN lo AND hi around the tuple (the library's
+ * own): rolling sums, minima and maxima over the last k rows or the last t
+ * key units, LAG and LEAD, the group's total per tuple.  The work per row does
+ * not depend on the frame's width.
+ * Groups: smj_dev_window's.  h(i) is the last group head at or before i, e(i)
+ *   the last position of i's group (one before the next group head, or n - 1).
+ *   group_shift is 0..63; values above 63 abort with a message.
+ * unit SMJ_FRAME_ROWS: the frame of row i is the positions j in [h(i), e(i)]
+ *   with i + lo <= j <= i + hi, the sums taken without wrap-around.
+ *   lo = INT64_MIN is UNBOUNDED PRECEDING, hi = INT64_MAX UNBOUNDED FOLLOWING.
+ *   Total: defined by position on any input, the run-length form included.
+ * unit SMJ_FRAME_RANGE: the frame of row i is the positions j in [h(i), e(i)]
+ *   with key[i] + lo <= key[j] <= key[i] + hi.  The keys are widened to int64
+ *   and the sums saturate at the ends of int64, exactly as in
+ *   smj_dev_band_join; a band that lies wholly outside int64 is empty.  The
+ *   band holds every peer (equal key) of i that it holds at all.  Requires
+ *   non-decreasing keys inside each group; on other input the rows of such a
+ *   group are unspecified, but the call still terminates, reads only
+ *   sorted[0..n) and writes only rows 0..n-1.
+ *   Any other unit aborts with a message.
+ * Empty frames: lo > hi makes every frame empty; a frame can also be empty on
+ *   its own (lo > 0 at a group's end, hi < 0 at its start, no key in the
+ *   band).  An empty frame writes the library's NULL: -1 in start_out, 0 in
+ *   every other column.
+ * Rows: every non-NULL column gets all n rows; row i belongs to sorted[i].
+ *   With the frame [a, b]:
+ *   start_out[i] = a.
+ *   count_out[i] = b - a + 1.
+ *   sum_out[i]   = the sum of the payloads of sorted[a .. b] as int64 modulo
+ *                  2^64 (the 8-byte library sign-extends its int32 payloads
+ *                  first).
+ *   min_out[i], max_out[i] = their signed minimum and maximum.
+ *   first_out[i], last_out[i] = the payloads of sorted[a] and sorted[b].
+ *   LAG(k) is first_out with ROWS lo = hi = -k, LEAD(k) with lo = hi = k, and
+ *   the value is NULL where count_out is 0.  ROWS (INT64_MIN, 0) gives
+ *   smj_dev_window's sum, minimum and maximum; RANGE (INT64_MIN, 0) is SQL's
+ *   default frame, peers sharing the value of their last row; ROWS
+ *   (INT64_MIN, INT64_MAX) is the group's total per tuple.
+ * Output: nothing is written beyond row n - 1.  n == 0, or all seven columns
+ *   NULL, launches nothing.  Stream-ordered like smj_dev_window: no host
+ *   synchronisation (the workspace's tables grow on a first call).
+ * Workspace: beside 64 bytes per 1024 tuples, a call holds per tuple 8 bytes
+ *   for sum_out and, for each of min_out and max_out, 2 * sizeof(value_t) and
+ *   another 3 * sizeof(value_t) per 64 tuples and (1 + log2(n / 1024)) *
+ *   sizeof(value_t) per 1024: with all three columns about 25 bytes per tuple
+ *   in the 8-byte library and 41 in the 16-byte one, and next to nothing for
+ *   a call without them.
+ * Buffers: the input is left untouched; the outputs must not overlap it or
+ *   each other.  Alignment as for the rest of the device API: any
+ *   tuple-granular slice of a hipMalloc buffer (for the 8-byte library also
+ *   one at an address that is 8 mod 16), columns aligned to their element.
+ *   n may exceed 2^32. */
+#define SMJ_FRAME_ROWS  0u
+#define SMJ_FRAME_RANGE 1u
+void smj_dev_window_frame(smj_workspace * ws, const tuple_t * sorted, uint64_t n,
+                          uint32_t group_shift, uint32_t unit, int64_t lo, int64_t hi,
+                          int64_t * start_out /* may be NULL */,
+                          int64_t * count_out /* may be NULL */,
+                          int64_t * sum_out   /* may be NULL */,
+                          value_t * min_out   /* may be NULL */,
+                          value_t * max_out   /* may be NULL */,
+                          value_t * first_out /* may be NULL */,
+                          value_t * last_out  /* may be NULL */,
+                          smj_stream_t stream);
+
+/* Elements of `sorted` one workgroup of the frame kernels' write pass handles
+ * (for tests; a host call, no device needed). */
+uint32_t smj_frame_tile(void);
+
+/* The inner aligned block of the frame kernels' range minimum and maximum: it
+ * divides smj_frame_tile() (for tests; a host call, no device needed). */
+uint32_t smj_frame_block(void);
+
 /* The m-way join on one device.  R and S are left untouched; sortedR/sortedS
  * (n tuples each) receive the fully sorted relations; the match count is
  * written to *count_dev.  key_min <= key_max is an optional hint of the key
