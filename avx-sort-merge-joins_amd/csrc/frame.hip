@@ -29,7 +29,7 @@
 //   k_frame_scan  small kernels over the tile tables: one scan over the tiles
 //                 carries the sums and the last head forward and, on the
 //                 mirrored index, the first head backward (sum, max and min
-//                 commute, so one two-level scan in gc_block_scan's shape does
+//                 commute, so one instance of ga_common.hpp's carry step does
 //                 all three); then the sparse table, a launch a level.  A call
 //                 without aggregates has no build pass, and the step's first
 //                 kernel takes the tiles' heads from the keys itself;
@@ -78,7 +78,6 @@ struct FCarry {
 // the workspace's tables of one call; those no asked column needs are null
 struct FrameTab {
     uint64_t ntiles;
-    uint32_t nb;      // workgroups of the scan step
     uint32_t levels;  // of the sparse table, level 0 being the tiles themselves
     int64_t *tsum, *texcl;      // per tile: its sum, the sum of the tiles in front
     int64_t *tlast, *hprev;     // its last head (-1), the last head in front of it
@@ -138,7 +137,7 @@ __device__ __forceinline__ void frame_build_tile(const Tup* __restrict__ in, uin
         for (int j = 0; j < GA_IPT; j++) {
             const uint64_t gi = cb + 64 * j + lane;
             const bool in_rel = gi < n;
-            const GAgg v = in_rel ? GAgg{(int64_t)pay[j], pay[j], pay[j]} : ga_none();
+            const GAgg v = in_rel ? ga_one(pay[j]) : ga_none();
             const GAgg p = ga_seg_scan(v, lane);  // the prefix over the block
             pre[j] = (int64_t)((uint64_t)run.sum + (uint64_t)p.sum);
             const GAgg all{last_lane(p.sum), last_lane(p.mn), last_lane(p.mx)};
@@ -236,83 +235,45 @@ k_frame_scan_heads(const Tup* __restrict__ in, uint64_t n, uint32_t gsh, FrameTa
     frame_build_tile<0>(in, n, gsh, g, L);
 }
 
-__device__ __forceinline__ FCarry fc_none() { return FCarry{0, -1, kNoHead}; }
-
-__device__ __forceinline__ FCarry fc_comb(const FCarry& a, const FCarry& b) {
-    return FCarry{(int64_t)((uint64_t)a.sum + (uint64_t)b.sum), vmax(a.last, b.last),
-                  vmin(a.first, b.first)};
-}
-
-// item x of the scan: tile x of the forward fields, tile ntiles - 1 - x of the
-// backward one
-__device__ __forceinline__ FCarry fc_load(const FrameTab& g, uint64_t x) {
-    if (x >= g.ntiles) return fc_none();
-    return FCarry{g.tsum ? g.tsum[x] : 0, g.tlast[x], g.tfirst[g.ntiles - 1 - x]};
-}
-
-// gc_block_scan over FCarry
-__device__ __forceinline__ FCarry fc_block_scan(FCarry v, FCarry* wl, FCarry* total) {
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        FCarry y;
+struct FCarryOps {
+    typedef FCarry T;
+    typedef CarryShared<FCarry> Shared;
+    static __device__ __forceinline__ T none() { return FCarry{0, -1, kNoHead}; }
+    static __device__ __forceinline__ T comb(const T& a, const T& b) {
+        return FCarry{(int64_t)((uint64_t)a.sum + (uint64_t)b.sum), vmax(a.last, b.last),
+                      vmin(a.first, b.first)};
+    }
+    static __device__ __forceinline__ T up(const T& v, int o) {
+        T y;
         y.sum = sh_up(v.sum, o);
         y.last = sh_up(v.last, o);
         y.first = (uint64_t)sh_up((int64_t)v.first, o);
-        if (lane >= o) v = fc_comb(y, v);
+        return y;
     }
-    if (lane == 63) wl[wid] = v;
-    __syncthreads();
-    FCarry p = fc_none(), all = fc_none();
-#pragma unroll 1  // as in gc_block_scan
-    for (int x = 0; x < (int)(GC_BLOCK / 64); x++) {
-        if (x == wid) p = all;
-        all = fc_comb(all, wl[x]);
-    }
-    *total = all;
-    __syncthreads();  // wl is free again
-    return fc_comb(p, v);
-}
+};
 
-// per GC_BLOCK items: their combination
-__global__ void __launch_bounds__(GC_BLOCK) k_frame_scan_part(FrameTab g) {
-    __shared__ FCarry wl[GC_BLOCK / 64];
-    FCarry all;
-    fc_block_scan(fc_load(g, (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x), wl, &all);
-    if (threadIdx.x == 0) g.part[blockIdx.x] = all;
-}
-
-// pexcl[b] = the parts in front of workgroup b combined (one workgroup)
-__global__ void __launch_bounds__(GC_BLOCK) k_frame_scan_pscan(FrameTab g) {
-    __shared__ FCarry wl[GC_BLOCK / 64];
-    FCarry run = fc_none();
-    if (threadIdx.x == 0) g.pexcl[0] = run;
-    for (uint32_t r0 = 0; r0 < g.nb; r0 += GC_BLOCK) {
-        const uint32_t b = r0 + threadIdx.x;
-        FCarry all;
-        const FCarry inc = fc_block_scan(b < g.nb ? g.part[b] : fc_none(), wl, &all);
-        if (b + 1 < g.nb) g.pexcl[b + 1] = fc_comb(run, inc);
-        run = fc_comb(run, all);
+// item x of the scan: tile x of the forward fields, tile ntiles - 1 - x of the
+// backward one
+struct FTiles {
+    const int64_t *tsum, *tlast;
+    const uint64_t* tfirst;
+    uint64_t ntiles;
+    __device__ __forceinline__ FCarry load(uint64_t x) const {
+        return FCarry{tsum ? tsum[x] : 0, tlast[x], tfirst[ntiles - 1 - x]};
     }
-}
+};
 
 // what lies in front of item x into the tables of its tiles
-__device__ __forceinline__ void fc_store(const FrameTab& g, uint64_t n, uint64_t x,
-                                         const FCarry& v) {
-    if (g.texcl) g.texcl[x] = v.sum;
-    g.hprev[x] = v.last;
-    g.hnext[g.ntiles - 1 - x] = v.first == kNoHead ? n : v.first;
-}
-
-__global__ void __launch_bounds__(GC_BLOCK) k_frame_scan_down(FrameTab g, uint64_t n) {
-    __shared__ FCarry wl[GC_BLOCK / 64];
-    const uint64_t x = (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x;
-    FCarry all;
-    const FCarry inc = fc_block_scan(fc_load(g, x), wl, &all);
-    const FCarry front = g.pexcl[blockIdx.x];
-    if (x == 0) fc_store(g, n, 0, front);
-    if (x + 1 < g.ntiles) fc_store(g, n, x + 1, fc_comb(front, inc));
-}
+struct FFronts {
+    int64_t *texcl, *hprev;
+    uint64_t* hnext;
+    uint64_t ntiles, n;
+    __device__ __forceinline__ void store(uint64_t x, const FCarry& v) const {
+        if (texcl) texcl[x] = v.sum;
+        hprev[x] = v.last;
+        hnext[ntiles - 1 - x] = v.first == kNoHead ? n : v.first;
+    }
+};
 
 // level k of the sparse table from level k - 1: entry t = tiles [t, t + 2^k)
 // (entries whose range leaves the relation are never read)
@@ -328,26 +289,12 @@ __global__ void __launch_bounds__(256) k_frame_scan_sparse(FrameTab g, uint32_t 
 
 // ---- the write pass
 
-// The searches of a RANGE end, with index type I: 32-bit offsets into the
-// tile's staged keys, where most ends lie, and 64-bit positions in the
-// relation.  K(i) = key i; before(x): key x lies in front of the answer.
+// The searches of a RANGE end are mat_common.hpp's, on 32-bit offsets into the
+// tile's staged keys, where most ends lie, and on positions in the relation.
 
-template <bool UPPER>
-__device__ __forceinline__ bool key_before(int64_t x, int64_t k) {
-    return UPPER ? x <= k : x < k;
-}
-
-// first index of [lo, hi) whose key is not before k (hi: none)
-template <bool UPPER, class I, class K>
-__device__ __forceinline__ I fr_search(K key, I lo, I hi, int64_t k) {
-    while (lo < hi) {
-        const I m = lo + ((hi - lo) >> 1);
-        if (key_before<UPPER>(key(m), k)) lo = m + 1; else hi = m;
-    }
-    return lo;
-}
-
-// the same answer, galloping forward from lo
+// key_gallop with one search behind the loop (written out: through key_gallop
+// the RANGE write kernels took 44 VGPRs for 38, and key_gallop in this form
+// changed the registers of the join-output kernels)
 template <bool UPPER, class I, class K>
 __device__ __forceinline__ I fr_gallop(K key, I lo, I hi, int64_t k) {
     I step = 1;
@@ -355,24 +302,8 @@ __device__ __forceinline__ I fr_gallop(K key, I lo, I hi, int64_t k) {
         lo += step;
         step <<= 1;
     }
-    return fr_search<UPPER>(key, lo, hi - lo >= step ? lo + step - 1 : hi, k);
+    return key_search<UPPER, I>(key, lo, hi - lo >= step ? lo + step - 1 : hi, k);
 }
-
-// the same answer, galloping backward from hi
-template <bool UPPER, class I, class K>
-__device__ __forceinline__ I fr_gallop_back(K key, I lo, I hi, int64_t k) {
-    I step = 1;
-    while (hi - lo >= step && !key_before<UPPER>(key(hi - step), k)) {
-        hi -= step;
-        step <<= 1;
-    }
-    return fr_search<UPPER>(key, hi - lo >= step ? hi - step + 1 : lo, hi, k);
-}
-
-struct LdsKey32 {
-    const int64_t* a;
-    __device__ __forceinline__ int64_t operator()(uint32_t i) const { return a[i]; }
-};
 
 // The first position of [from, to) whose key is not before k (to: none), for a
 // row of the tile [tb, te) with tb < from <= te: inside the tile when its last
@@ -384,7 +315,7 @@ __device__ __forceinline__ uint64_t frame_end_fwd(const Tup* __restrict__ in, co
                                                   uint64_t to, int64_t k) {
     const uint64_t tl = to < te ? to : te;
     if (from < tl && !key_before<UPPER>(lkey[tl - 1 - tb], k))
-        return tb + fr_gallop<UPPER>(LdsKey32{lkey}, (uint32_t)(from - tb), (uint32_t)(tl - tb), k);
+        return tb + fr_gallop<UPPER>(LdsKey{lkey}, (uint32_t)(from - tb), (uint32_t)(tl - tb), k);
     if (to <= te) return to;
     if (key_before<UPPER>(ga_key(in + to - 1), k)) return to;
     return fr_gallop<UPPER>(TupKey{in}, te, to, k);
@@ -398,11 +329,11 @@ __device__ __forceinline__ uint64_t frame_end_back(const Tup* __restrict__ in, c
                                                    int64_t k) {
     const uint64_t fl = lo > tb ? lo : tb;
     if (fl < hi && key_before<UPPER>(lkey[fl - tb], k))
-        return tb + fr_gallop_back<UPPER>(LdsKey32{lkey}, (uint32_t)(fl + 1 - tb),
-                                          (uint32_t)(hi - tb), k);
+        return tb + key_gallop_back<UPPER, uint32_t>(LdsKey{lkey}, (uint32_t)(fl + 1 - tb),
+                                                     (uint32_t)(hi - tb), k);
     if (lo >= tb) return fl;
     if (!key_before<UPPER>(ga_key(in + lo), k)) return lo;
-    return fr_gallop_back<UPPER>(TupKey{in}, lo, tb, k);
+    return key_gallop_back<UPPER>(TupKey{in}, lo, tb, k);
 }
 
 template <int AGG, bool RANGE>
@@ -543,7 +474,7 @@ k_frame_write(const Tup* __restrict__ in, uint64_t n, uint32_t gsh, int64_t lo, 
 static FrameTab frame_tab(Workspace* ws, uint64_t n, const FrameCols& cols) {
     FrameTab g = {};
     g.ntiles = (n + GA_TILE - 1) / GA_TILE;
-    g.nb = (uint32_t)((g.ntiles + GC_BLOCK - 1) / GC_BLOCK);
+    const size_t nb = (size_t)((g.ntiles + GC_BLOCK - 1) / GC_BLOCK);  // scan workgroups
     g.levels = 1;
     while ((2ull << (g.levels - 1)) <= g.ntiles) g.levels++;
     const uint64_t nblocks = (n + FR_BLOCK - 1) / FR_BLOCK;
@@ -558,7 +489,7 @@ static FrameTab frame_tab(Workspace* ws, uint64_t n, const FrameCols& cols) {
     const size_t o_tsum = take(sum ? tile8 : 0), o_texcl = take(sum ? tile8 : 0);
     const size_t o_tlast = take(tile8), o_hprev = take(tile8);
     const size_t o_tfirst = take(tile8), o_hnext = take(tile8);
-    const size_t o_part = take(g.nb * sizeof(FCarry)), o_pexcl = take(g.nb * sizeof(FCarry));
+    const size_t o_part = take(nb * sizeof(FCarry)), o_pexcl = take(nb * sizeof(FCarry));
     const size_t o_pre = take(sum ? n * 8 : 0);
     const size_t el = n * sizeof(MatVal), bl = nblocks * sizeof(MatVal);
     const size_t sp = (size_t)g.levels * g.ntiles * sizeof(MatVal);
@@ -613,12 +544,9 @@ static void frame_passes(Workspace* ws, const Tup* in, uint64_t n, uint32_t gsh,
             hipLaunchKernelGGL(k_frame_scan_heads, grid, block, 0, st, in, n, gsh, g);
             SMJ_CHECK(hipGetLastError());
         }
-        hipLaunchKernelGGL(k_frame_scan_part, dim3(g.nb), dim3(GC_BLOCK), 0, st, g);
-        SMJ_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_frame_scan_pscan, dim3(1), dim3(GC_BLOCK), 0, st, g);
-        SMJ_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_frame_scan_down, dim3(g.nb), dim3(GC_BLOCK), 0, st, g, n);
-        SMJ_CHECK(hipGetLastError());
+        carry_scan<FCarryOps>(ws, nullptr, FTiles{g.tsum, g.tlast, g.tfirst, g.ntiles}, g.ntiles,
+                              CarryTable<FCarry>{g.part}, CarryTable<FCarry>{g.pexcl},
+                              FFronts{g.texcl, g.hprev, g.hnext, g.ntiles, n}, st);
         if (AGG == 2) {
             for (uint32_t k = 1; k < g.levels; k++) {
                 hipLaunchKernelGGL(k_frame_scan_sparse, dim3((uint32_t)((g.ntiles + 255) / 256)),
@@ -628,12 +556,10 @@ static void frame_passes(Workspace* ws, const Tup* in, uint64_t n, uint32_t gsh,
         }
     }
     TraceScope ts(ws, "k_frame_write", st);
-    if (range)
-        hipLaunchKernelGGL((k_frame_write<AGG, true>), grid, block, 0, st, in, n, gsh, lo, hi, g,
-                           cols);
-    else
-        hipLaunchKernelGGL((k_frame_write<AGG, false>), grid, block, 0, st, in, n, gsh, lo, hi, g,
-                           cols);
+    with_flag(range, [&](auto R) {
+        hipLaunchKernelGGL((k_frame_write<AGG, decltype(R)::value>), grid, block, 0, st, in, n,
+                           gsh, lo, hi, g, cols);
+    });
     SMJ_CHECK(hipGetLastError());
 }
 
@@ -645,9 +571,9 @@ void window_frame(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift
                          (MatVal*)first_out, (MatVal*)last_out};
     const int agg = (cols.mn || cols.mx) ? 2 : cols.sum ? 1 : 0;
     if (n == 0 || !(agg || cols.start || cols.count || cols.first || cols.last)) return;
-    if (agg == 2) frame_passes<2>(ws, in, n, group_shift, range, lo, hi, cols, st);
-    else if (agg == 1) frame_passes<1>(ws, in, n, group_shift, range, lo, hi, cols, st);
-    else frame_passes<0>(ws, in, n, group_shift, range, lo, hi, cols, st);
+    with_agg(agg, [&](auto A) {
+        frame_passes<decltype(A)::value>(ws, in, n, group_shift, range, lo, hi, cols, st);
+    });
 }
 
 }  // namespace smj

@@ -39,8 +39,11 @@
 // shift the first key of a run is not the key of its end: the end reads it
 // from the relation at the run's start (one key per row, not a pass).
 // smj_dev_group_count is the count pass over the keys alone and a reduction.
-// What window.hip's kernels use as well (the geometry, GAgg and GCarry, the
-// lane moves, ga_load, ga_seg_scan, gc_block_scan) lies in ga_common.hpp.
+// What window.hip and frame.hip use as well lies in ga_common.hpp: the
+// geometry, GAgg and GCarry, the lane moves, ga_load, ga_seg_scan, the count
+// pass's wave (ga_wave_tail), the write pass's chunk walk (ga_walk,
+// ga_incoming), the carry step (k_carry_*, of which tail_carry() here is the
+// GCarry instance, window.hip's too) and the table (tail_tab).
 #include "smj_common.hpp"
 #include "smj_internal.hpp"
 #include "mat_common.hpp"
@@ -60,11 +63,6 @@ struct GroupCols {
     MatVal* mx;
 };
 
-struct GWave {  // what a wave leaves for the others of its tile
-    GCarry tail;
-    uint32_t heads;
-};
-
 // AGG 0: the tails' head positions alone (tail may be null: the count form),
 // 1: with their sums, 2: with minimum and maximum as well (what nobody asks
 // for is not computed: the scans are what the passes spend their time on).
@@ -73,39 +71,17 @@ __global__ void __launch_bounds__(GA_THREADS)
 k_group_count(const Tup* __restrict__ in, uint64_t n, uint32_t gsh, uint64_t* __restrict__ cnt,
               GCarry* __restrict__ tail) {
     __shared__ GWave L[GA_WAVES];
-    const int lane = lane_id(), w = threadIdx.x >> 6;
+    const int w = threadIdx.x >> 6;
     const uint64_t cb = (uint64_t)blockIdx.x * GA_TILE + (uint64_t)w * GA_CHUNK;
     int64_t key[GA_IPT];
     MatVal pay[GA_IPT];
     uint64_t hb[GA_IPT];
     ga_load<AGG != 0>(in, n, cb, gsh, key, pay, hb);
-    uint32_t heads = 0;
-    uint64_t lstart = kNoHead;  // the chunk's last head
-#pragma unroll
-    for (int j = 0; j < GA_IPT; j++) {
-        heads += (uint32_t)__popcll(hb[j]);
-        if (hb[j]) lstart = cb + 64 * j + top_bit(hb[j]);
-    }
-    GAgg a = ga_none();
-    if (AGG) {
-#pragma unroll
-        for (int j = 0; j < GA_IPT; j++) {
-            const uint64_t gi = cb + 64 * j + lane;
-            // behind the last head, or everything (kNoHead is above every gi)
-            const bool in_tail = gi < n && (lstart == kNoHead || gi >= lstart);
-            if (in_tail) a = ga_comb(a, GAgg{(int64_t)pay[j], pay[j], pay[j]});
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-            a = ga_comb(a, GAgg{sh_xor(a.sum, o), sh_xor(a.mn, o), sh_xor(a.mx, o)});
-    }
-    if (lane == 0) {
-        L[w].tail = GCarry{a.sum, AGG == 2 ? (int64_t)a.mn : 0, AGG == 2 ? (int64_t)a.mx : 0,
-                           lstart};
-        L[w].heads = heads;
-    }
+    ga_wave_tail<AGG>(n, cb, pay, hb, &L[w]);
     __syncthreads();
     if (threadIdx.x == 0) {
+        // (written out: through a shared fold of the waves, k_group_count<0> took 27
+        // VGPRs for 26 and k_window_count<0, true> 34 for 32 at 8-byte tuples)
         GCarry t = gc_none();
         uint64_t h = 0;
 #pragma unroll
@@ -116,46 +92,6 @@ k_group_count(const Tup* __restrict__ in, uint64_t n, uint32_t gsh, uint64_t* __
         cnt[blockIdx.x] = h;
         if (tail) tail[blockIdx.x] = t;
     }
-}
-
-// ---- the carry step: a segmented scan of the tails over the tiles
-
-// per GC_BLOCK tiles: their tails combined
-__global__ void __launch_bounds__(GC_BLOCK)
-k_group_carry_part(const GCarry* __restrict__ tail, uint64_t ntiles, GCarry* __restrict__ part) {
-    __shared__ GCarry wl[GC_BLOCK / 64];
-    const uint64_t t = (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x;
-    GCarry all;
-    gc_block_scan(t < ntiles ? tail[t] : gc_none(), wl, &all);
-    if (threadIdx.x == 0) part[blockIdx.x] = all;
-}
-
-// pexcl[b] = the parts in front of workgroup b combined (one workgroup)
-__global__ void __launch_bounds__(GC_BLOCK)
-k_group_carry_pscan(const GCarry* __restrict__ part, uint32_t nb, GCarry* __restrict__ pexcl) {
-    __shared__ GCarry wl[GC_BLOCK / 64];
-    GCarry run = gc_none();
-    if (threadIdx.x == 0) pexcl[0] = run;
-    for (uint32_t r0 = 0; r0 < nb; r0 += GC_BLOCK) {
-        const uint32_t b = r0 + threadIdx.x;
-        GCarry all;
-        const GCarry inc = gc_block_scan(b < nb ? part[b] : gc_none(), wl, &all);
-        if (b + 1 < nb) pexcl[b + 1] = gc_comb(run, inc);
-        run = gc_comb(run, all);
-    }
-}
-
-// carry[t] = the tails of all tiles in front of tile t combined
-__global__ void __launch_bounds__(GC_BLOCK)
-k_group_carry_down(const GCarry* __restrict__ tail, uint64_t ntiles,
-                   const GCarry* __restrict__ pexcl, GCarry* __restrict__ carry) {
-    __shared__ GCarry wl[GC_BLOCK / 64];
-    const uint64_t t = (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x;
-    GCarry all;
-    const GCarry inc = gc_block_scan(t < ntiles ? tail[t] : gc_none(), wl, &all);
-    const GCarry front = pexcl[blockIdx.x];
-    if (t == 0) carry[0] = front;
-    if (t + 1 < ntiles) carry[t + 1] = gc_comb(front, inc);
 }
 
 // AGG 0: key, start and count alone, 1: the sum too, 2: minimum and maximum too
@@ -171,7 +107,6 @@ k_group_write(const Tup* __restrict__ in, uint64_t n, uint32_t gsh,
     if (row0 > out_cap) return;
     const int lane = lane_id(), w = threadIdx.x >> 6;
     const uint64_t cb = (uint64_t)blockIdx.x * GA_TILE + (uint64_t)w * GA_CHUNK;
-    const uint64_t le = lanemask_le();
     int64_t key[GA_IPT];
     MatVal pay[GA_IPT];
     uint64_t hb[GA_IPT];
@@ -181,45 +116,14 @@ k_group_write(const Tup* __restrict__ in, uint64_t n, uint32_t gsh,
     bool next_head = ce == n;
     if (ce < n) next_head = (ga_key(in + ce) >> gsh) != (ga_key(in + ce - 1) >> gsh);
 
-    GAgg x[GA_IPT];        // aggregate from the element's head, or the chunk's start, to it
-    uint64_t st[GA_IPT];   // that head's position; kNoHead: in front of the chunk
-    uint32_t hrank[GA_IPT];  // heads of the chunk at or before the element
-    GAgg run = ga_none();  // the open tail of the rounds so far
-    uint64_t rstart = kNoHead;
-    uint32_t heads = 0;
-#pragma unroll
-    for (int j = 0; j < GA_IPT; j++) {
-        const uint64_t rb = cb + 64 * j;
-        const uint64_t hm = hb[j] & le;  // the round's heads at or before this lane
-        const uint32_t seg = hm ? top_bit(hm) : 0;
-        if (AGG) {
-            GAgg v = rb + lane < n ? GAgg{(int64_t)pay[j], pay[j], pay[j]} : ga_none();
-            v = ga_seg_scan(v, lane - (int)seg);
-            if (!hm) v = ga_comb(run, v);
-            x[j] = v;
-            run = GAgg{last_lane(v.sum), last_lane(v.mn), last_lane(v.mx)};
-        }
-        st[j] = hm ? rb + seg : rstart;
-        if (hb[j]) rstart = rb + top_bit(hb[j]);
-        hrank[j] = heads + (uint32_t)__popcll(hm);
-        heads += (uint32_t)__popcll(hb[j]);
-    }
-    if (lane == 0) {
-        L[w].tail = GCarry{run.sum, AGG == 2 ? (int64_t)run.mn : 0, AGG == 2 ? (int64_t)run.mx : 0,
-                           rstart};
-        L[w].heads = heads;
-    }
+    GAgg x[GA_IPT];
+    uint32_t so[GA_IPT], hrank[GA_IPT];
+    const GWave mine = ga_walk<AGG>(n, cb, pay, hb, x, so, hrank);
+    if (lane == 0) L[w] = mine;
     __syncthreads();
-    // what comes in from the earlier tiles and the earlier waves of this one
     GCarry inc = carry[blockIdx.x];
     uint64_t row = row0;
-#pragma unroll
-    for (int v = 0; v < GA_WAVES - 1; v++) {
-        if (v < w) {
-            inc = gc_comb(inc, L[v].tail);
-            row += L[v].heads;
-        }
-    }
+    ga_incoming(L, w, inc, row);
     const GAgg ia{inc.sum, (MatVal)inc.mn, (MatVal)inc.mx};
 #pragma unroll
     for (int j = 0; j < GA_IPT; j++) {
@@ -234,8 +138,8 @@ k_group_write(const Tup* __restrict__ in, uint64_t n, uint32_t gsh,
         if (!((eb >> lane) & 1) || gi >= n) continue;
         const uint64_t r = row + hrank[j] - 1;  // element 0 is a head: no row below 0
         if (r >= out_cap) continue;
-        const bool far = st[j] == kNoHead;
-        const uint64_t s = far ? inc.start : st[j];
+        const bool far = so[j] == kNoOff;
+        const uint64_t s = far ? inc.start : cb + so[j];
         if (cols.key) {
             int64_t k = key[j];
             if (gsh != 0 && s < gi) k = ga_key(in + s);  // s <= gi < n
@@ -252,31 +156,15 @@ k_group_write(const Tup* __restrict__ in, uint64_t n, uint32_t gsh,
     }
 }
 
-// materialize.hip's tile table with 0 bounds words (`bounds` is unused and
-// equals `tot`) and, in tile_tab's extra bytes behind tot[0..1], the carry
-// step's tables
-struct GroupTab : TileTab {
-    uint32_t nb;  // workgroups of the carry step
-    GCarry *tail, *carry, *part, *pexcl;
-};
-
-static GroupTab group_tab(Workspace* ws, uint64_t n) {
-    GroupTab g;
-    const uint64_t ntiles = (n + GA_TILE - 1) / GA_TILE;
-    g.nb = (uint32_t)((ntiles + GC_BLOCK - 1) / GC_BLOCK);
-    const size_t pad = ((3 * ntiles) & 1) * 8;  // the GCarry tables 16-aligned
-    static_cast<TileTab&>(g) = tile_tab(
-        ws, "group_tab", ntiles, 0, pad + (2 * ntiles + 2 * (size_t)g.nb) * sizeof(GCarry));
-    g.tail = (GCarry*)((char*)(g.tot + 2) + pad);
-    g.carry = g.tail + g.ntiles;
-    g.part = g.carry + g.ntiles;
-    g.pexcl = g.part + g.nb;
-    return g;
+void tail_carry(Workspace* ws, const char* name, const TailTab& g, hipStream_t st) {
+    typedef CarryTable<GCarry> Tab;
+    carry_scan<GCarryOps>(ws, name, Tab{g.tail}, g.ntiles, Tab{g.part}, Tab{g.pexcl},
+                          Tab{g.carry}, st);
 }
 
 template <int AGG>
 static void group_count_pass(Workspace* ws, const Tup* in, uint64_t n, uint32_t gsh,
-                             const GroupTab& g, bool tails, hipStream_t st) {
+                             const TailTab& g, bool tails, hipStream_t st) {
     TraceScope ts(ws, "k_group_count", st);
     hipLaunchKernelGGL(k_group_count<AGG>, dim3((uint32_t)g.ntiles), dim3(GA_THREADS), 0, st, in,
                        n, gsh, g.cnt, tails ? g.tail : nullptr);
@@ -292,37 +180,22 @@ uint64_t group_aggregate(Workspace* ws, const Tup* in, uint64_t n, uint32_t grou
                          (MatVal*)max_out};
     const int agg = (cols.mn || cols.mx) ? 2 : cols.sum ? 1 : 0;
     const bool rows = out_cap && (agg || cols.key || cols.start || cols.count);
-    const GroupTab g = group_tab(ws, n);
-    if (rows && agg == 2) group_count_pass<2>(ws, in, n, group_shift, g, true, st);
-    else if (rows && agg == 1) group_count_pass<1>(ws, in, n, group_shift, g, true, st);
-    else group_count_pass<0>(ws, in, n, group_shift, g, rows, st);
+    const TailTab g = tail_tab(ws, "group_tab", n, false);
+    // without rows, the count form
+    with_agg(rows ? agg : 0, [&](auto A) {
+        group_count_pass<decltype(A)::value>(ws, in, n, group_shift, g, rows, st);
+    });
     mat_scan(ws, g.cnt, g.ntiles, g.base, g.ibase, g.tot, st);
     if (rows) {
-        {
-            TraceScope ts(ws, "k_group_carry", st);
-            hipLaunchKernelGGL(k_group_carry_part, dim3(g.nb), dim3(GC_BLOCK), 0, st, g.tail,
-                               g.ntiles, g.part);
-            SMJ_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_group_carry_pscan, dim3(1), dim3(GC_BLOCK), 0, st, g.part, g.nb,
-                               g.pexcl);
-            SMJ_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_group_carry_down, dim3(g.nb), dim3(GC_BLOCK), 0, st, g.tail,
-                               g.ntiles, g.pexcl, g.carry);
-            SMJ_CHECK(hipGetLastError());
-        }
+        tail_carry(ws, "k_group_carry", g, st);
         // every tile is launched: those whose rows lie at out_cap and above
         // leave at once, so the launch needs no count on the host
         TraceScope ts(ws, "k_group_write", st);
-        const dim3 grid((uint32_t)g.ntiles), block(GA_THREADS);
-        if (agg == 2)
-            hipLaunchKernelGGL(k_group_write<2>, grid, block, 0, st, in, n, group_shift, g.base,
-                               g.carry, cols, out_cap);
-        else if (agg == 1)
-            hipLaunchKernelGGL(k_group_write<1>, grid, block, 0, st, in, n, group_shift, g.base,
-                               g.carry, cols, out_cap);
-        else
-            hipLaunchKernelGGL(k_group_write<0>, grid, block, 0, st, in, n, group_shift, g.base,
-                               g.carry, cols, out_cap);
+        with_agg(agg, [&](auto A) {
+            hipLaunchKernelGGL(k_group_write<decltype(A)::value>, dim3((uint32_t)g.ntiles),
+                               dim3(GA_THREADS), 0, st, in, n, group_shift, g.base, g.carry, cols,
+                               out_cap);
+        });
         SMJ_CHECK(hipGetLastError());
     }
     uint64_t* h = (uint64_t*)ws->host_pinned("group_tot_h", 16);
@@ -334,7 +207,7 @@ uint64_t group_aggregate(Workspace* ws, const Tup* in, uint64_t n, uint32_t grou
 void group_count(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift,
                  unsigned long long* groups_dev, hipStream_t st) {
     if (n == 0) return;
-    const GroupTab g = group_tab(ws, n);
+    const TailTab g = tail_tab(ws, "group_tab", n, false);
     group_count_pass<0>(ws, in, n, group_shift, g, false, st);
     tile_total(ws, "k_group_total", g.cnt, g.ntiles, groups_dev, st);
 }

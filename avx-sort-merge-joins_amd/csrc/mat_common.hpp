@@ -5,6 +5,7 @@
 // the walk over a tile's key runs with the per-tile bounds it starts from, and
 // the work-item prologue and the per-output searches of the write passes.
 #pragma once
+#include <type_traits>
 #include "smj_common.hpp"
 
 namespace smj {
@@ -56,14 +57,21 @@ __device__ __forceinline__ int64_t sat_add(int64_t k, int64_t d, int& over) {
     return r;
 }
 
-// first index of [lo, hi) whose key is >= k (UPPER: > k); K(i) = key i
-template <bool UPPER, class K>
-__device__ __forceinline__ uint64_t key_search(K key, uint64_t lo, uint64_t hi,
-                                               int64_t k) {
+// key x lies in front of the first key >= k (UPPER: > k)
+template <bool UPPER>
+__device__ __forceinline__ bool key_before(int64_t x, int64_t k) {
+    return UPPER ? x <= k : x < k;
+}
+
+// first index of [lo, hi) whose key is >= k (UPPER: > k), hi: none; K(i) = key
+// i.  I is the index type: positions in a relation, or 32-bit offsets into
+// staged keys (named by the caller, not deduced: common_type_t keeps it out)
+template <bool UPPER, class I = uint64_t, class K>
+__device__ __forceinline__ I key_search(K key, std::common_type_t<I> lo,
+                                        std::common_type_t<I> hi, int64_t k) {
     while (lo < hi) {
-        const uint64_t m = (lo + hi) >> 1;
-        const int64_t x = key(m);
-        if (UPPER ? x <= k : x < k) lo = m + 1; else hi = m;
+        const I m = (lo + hi) >> 1;
+        if (key_before<UPPER>(key(m), k)) lo = m + 1; else hi = m;
     }
     return lo;
 }
@@ -77,11 +85,22 @@ __device__ __forceinline__ uint64_t key_gallop(K key, uint64_t lo, uint64_t hi,
     while (true) {
         const uint64_t e = lo + step - 1;
         if (e >= hi) return key_search<UPPER>(key, lo, hi, k);
-        const int64_t x = key(e);
-        if (!(UPPER ? x <= k : x < k)) return key_search<UPPER>(key, lo, e, k);
+        if (!key_before<UPPER>(key(e), k)) return key_search<UPPER>(key, lo, e, k);
         lo = e + 1;
         step <<= 1;
     }
+}
+
+// the same answer, galloping backward from hi
+template <bool UPPER, class I = uint64_t, class K>
+__device__ __forceinline__ I key_gallop_back(K key, std::common_type_t<I> lo,
+                                             std::common_type_t<I> hi, int64_t k) {
+    I step = 1;
+    while (hi - lo >= step && !key_before<UPPER>(key(hi - step), k)) {
+        hi -= step;
+        step <<= 1;
+    }
+    return key_search<UPPER, I>(key, hi - lo >= step ? hi - step + 1 : lo, hi, k);
 }
 
 struct TupKey {

@@ -12,8 +12,11 @@
 // = the key heads in (h, i], which are the key heads that are no group heads
 // ("key-only" heads below).
 //
-// The passes are groupagg.hip's, with its geometry (ga_common.hpp): a group
-// spans any number of tiles and no workgroup waits for another.
+// The passes are groupagg.hip's, with its geometry and its shared pieces
+// (ga_common.hpp: ga_wave_tail, ga_walk, the carry step, tail_tab): a group
+// spans any number of tiles and no workgroup waits for another.  Without RANKS
+// the carry step is groupagg.hip's own (tail_carry); with RANKS it is the same
+// kernels over WCarry, the two levels in parallel tables.
 //   k_window_count one workgroup per tile: the tile's number of group heads
 //                  and its open tail -- groupagg.hip's GCarry, and with RANKS
 //                  the key level (KCarry): the position of its last key head
@@ -44,8 +47,6 @@ namespace smj {
 
 uint32_t window_tile() { return GA_TILE; }
 
-constexpr uint32_t kNoOff = ~0u;  // a head offset in the chunk: in front of it
-
 // the output columns (each may be null)
 struct WinCols {
     int64_t* group;
@@ -57,12 +58,7 @@ struct WinCols {
     MatVal* mx;
 };
 
-// the key level of an open tail: its last key head (kNoHead: none) and the
-// key-only heads behind its last group head (in all of it when it has none)
-struct KCarry {
-    uint64_t kstart, dense;
-};
-
+// the key level of an open tail is ga_common.hpp's KCarry
 __device__ __forceinline__ KCarry kc_none() { return KCarry{kNoHead, 0}; }
 
 // a then b; cut: b has a group head, which closes a's count as it closes a's
@@ -73,12 +69,6 @@ __device__ __forceinline__ KCarry kc_comb(const KCarry& a, const KCarry& b, bool
     r.dense = cut ? b.dense : a.dense + b.dense;
     return r;
 }
-
-struct WWave {  // what a wave leaves for the others of its tile
-    GCarry tail;
-    KCarry k;
-    uint32_t heads;
-};
 
 // per round the ballot of the key heads of the wave's chunk (ga_load's head
 // ballots with the whole key for the group)
@@ -101,59 +91,44 @@ __device__ __forceinline__ void wn_key_heads(const Tup* __restrict__ in, uint64_
 // the bits of m at and above bit b
 __device__ __forceinline__ uint64_t from_bit(uint64_t m, uint32_t b) { return m & (~0ull << b); }
 
+// groupagg.hip's count pass; with RANKS the key level beside it
 template <int AGG, bool RANKS>
 __global__ void __launch_bounds__(GA_THREADS)
 k_window_count(const Tup* __restrict__ in, uint64_t n, uint32_t gsh, uint64_t* __restrict__ cnt,
                GCarry* __restrict__ tail, KCarry* __restrict__ ktail) {
-    __shared__ WWave L[GA_WAVES];
-    const int lane = lane_id(), w = threadIdx.x >> 6;
+    __shared__ GWave L[GA_WAVES];
+    __shared__ KCarry LK[RANKS ? GA_WAVES : 1];
+    const int w = threadIdx.x >> 6;
     const uint64_t cb = (uint64_t)blockIdx.x * GA_TILE + (uint64_t)w * GA_CHUNK;
     int64_t key[GA_IPT];
     MatVal pay[GA_IPT];
-    uint64_t hb[GA_IPT], kb[GA_IPT];
+    uint64_t hb[GA_IPT];
     ga_load<AGG != 0>(in, n, cb, gsh, key, pay, hb);
-    if (RANKS) wn_key_heads(in, n, cb, key, kb);
-    uint32_t heads = 0;
-    uint64_t lstart = kNoHead, kstart = kNoHead;  // the chunk's last group head, key head
-    uint64_t dense = 0;                           // key-only heads behind lstart
-#pragma unroll
-    for (int j = 0; j < GA_IPT; j++) {
-        heads += (uint32_t)__popcll(hb[j]);
-        if (hb[j]) lstart = cb + 64 * j + top_bit(hb[j]);
-        if (RANKS) {
-            const uint64_t ko = kb[j] & ~hb[j];
-            if (hb[j]) dense = (uint64_t)__popcll(from_bit(ko, top_bit(hb[j])));
-            else dense += (uint64_t)__popcll(ko);
-            if (kb[j]) kstart = cb + 64 * j + top_bit(kb[j]);
-        }
-    }
-    GAgg a = ga_none();
-    if (AGG) {
+    if (RANKS) {
+        uint64_t kb[GA_IPT];
+        wn_key_heads(in, n, cb, key, kb);
+        uint32_t kso = kNoOff;  // the chunk's last key head
+        uint32_t dense = 0;     // key-only heads behind its last group head
 #pragma unroll
         for (int j = 0; j < GA_IPT; j++) {
-            const uint64_t gi = cb + 64 * j + lane;
-            // behind the last head, or everything (kNoHead is above every gi)
-            const bool in_tail = gi < n && (lstart == kNoHead || gi >= lstart);
-            if (in_tail) a = ga_comb(a, GAgg{(int64_t)pay[j], pay[j], pay[j]});
+            const uint64_t ko = kb[j] & ~hb[j];
+            if (hb[j]) dense = (uint32_t)__popcll(from_bit(ko, top_bit(hb[j])));
+            else dense += (uint32_t)__popcll(ko);
+            if (kb[j]) kso = 64 * j + top_bit(kb[j]);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-            a = ga_comb(a, GAgg{sh_xor(a.sum, o), sh_xor(a.mn, o), sh_xor(a.mx, o)});
+        if (lane_id() == 0) LK[w] = KCarry{kso == kNoOff ? kNoHead : cb + kso, dense};
     }
-    if (lane == 0) {
-        L[w].tail = GCarry{a.sum, AGG == 2 ? (int64_t)a.mn : 0, AGG == 2 ? (int64_t)a.mx : 0,
-                           lstart};
-        if (RANKS) L[w].k = KCarry{kstart, dense};
-        L[w].heads = heads;
-    }
+    ga_wave_tail<AGG>(n, cb, pay, hb, &L[w]);
     __syncthreads();
     if (threadIdx.x == 0) {
+        // (written out: through a shared fold of the waves, k_group_count<0> took 27
+        // VGPRs for 26 and k_window_count<0, true> 34 for 32 at 8-byte tuples)
         GCarry t = gc_none();
         KCarry k = kc_none();
         uint64_t h = 0;
 #pragma unroll
         for (int v = 0; v < GA_WAVES; v++) {
-            if (RANKS) k = kc_comb(k, L[v].k, L[v].tail.start != kNoHead);
+            if (RANKS) k = kc_comb(k, LK[v], L[v].tail.start != kNoHead);
             t = gc_comb(t, L[v].tail);
             h += L[v].heads;
         }
@@ -163,191 +138,98 @@ k_window_count(const Tup* __restrict__ in, uint64_t n, uint32_t gsh, uint64_t* _
     }
 }
 
-// ---- the carry step: groupagg.hip's, with the key level beside the tails
+// ---- the carry step with RANKS: both levels in one scan (without, the
+// tails alone: ga_common.hpp's tail_carry, groupagg.hip's kernels)
 
 struct WCarry {
     GCarry g;
     KCarry k;
 };
 
-template <bool RANKS>
-__device__ __forceinline__ WCarry wc_comb(const WCarry& a, const WCarry& b) {
-    WCarry r;
-    r.g = gc_comb(a.g, b.g);
-    r.k = RANKS ? kc_comb(a.k, b.k, b.g.start != kNoHead) : kc_none();
-    return r;
-}
-
-template <bool RANKS>
-__device__ __forceinline__ WCarry wc_load(const GCarry* g, const KCarry* k, uint64_t i, bool in) {
-    WCarry r;
-    r.g = in ? g[i] : gc_none();
-    r.k = RANKS && in ? k[i] : kc_none();
-    return r;
-}
-
-template <bool RANKS>
-__device__ __forceinline__ void wc_store(GCarry* g, KCarry* k, uint64_t i, const WCarry& v) {
-    g[i] = v.g;
-    if (RANKS) k[i] = v.k;
-}
-
-// gc_block_scan over both levels
-template <bool RANKS>
-__device__ __forceinline__ WCarry wc_block_scan(WCarry v, GCarry* wl, KCarry* wk, WCarry* total) {
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
+struct WCarryOps {
+    typedef WCarry T;
+    struct Shared {
+        GCarry g[GC_BLOCK / 64];
+        KCarry k[GC_BLOCK / 64];
+        __device__ __forceinline__ void put(int i, const T& v) { g[i] = v.g; k[i] = v.k; }
+        __device__ __forceinline__ T get(int i) const { return WCarry{g[i], k[i]}; }
+    };
+    static __device__ __forceinline__ T none() { return WCarry{gc_none(), kc_none()}; }
+    static __device__ __forceinline__ T comb(const T& a, const T& b) {
+        WCarry r;
+        r.g = gc_comb(a.g, b.g);
+        r.k = kc_comb(a.k, b.k, b.g.start != kNoHead);
+        return r;
+    }
+    static __device__ __forceinline__ T up(const T& v, int o) {
         WCarry y;
-        y.g.sum = sh_up(v.g.sum, o);
-        y.g.mn = sh_up(v.g.mn, o);
-        y.g.mx = sh_up(v.g.mx, o);
-        y.g.start = (uint64_t)sh_up((int64_t)v.g.start, o);
-        y.k = kc_none();
-        if (RANKS) {
-            y.k.kstart = (uint64_t)sh_up((int64_t)v.k.kstart, o);
-            y.k.dense = (uint64_t)sh_up((int64_t)v.k.dense, o);
-        }
-        if (lane >= o) v = wc_comb<RANKS>(y, v);
+        y.g = GCarryOps::up(v.g, o);
+        y.k.kstart = (uint64_t)sh_up((int64_t)v.k.kstart, o);
+        y.k.dense = (uint64_t)sh_up((int64_t)v.k.dense, o);
+        return y;
     }
-    if (lane == 63) {
-        wl[wid] = v.g;
-        if (RANKS) wk[wid] = v.k;
-    }
-    __syncthreads();
-    WCarry p{gc_none(), kc_none()}, all{gc_none(), kc_none()};
-#pragma unroll 1  // as in gc_block_scan
-    for (int x = 0; x < (int)(GC_BLOCK / 64); x++) {
-        if (x == wid) p = all;
-        WCarry e;
-        e.g = wl[x];
-        e.k = RANKS ? wk[x] : kc_none();
-        all = wc_comb<RANKS>(all, e);
-    }
-    *total = all;
-    __syncthreads();  // wl and wk are free again
-    return wc_comb<RANKS>(p, v);
-}
+};
 
-// per GC_BLOCK tiles: their tails combined
-template <bool RANKS>
-__global__ void __launch_bounds__(GC_BLOCK)
-k_window_carry_part(const GCarry* __restrict__ tail, const KCarry* __restrict__ ktail,
-                    uint64_t ntiles, GCarry* __restrict__ part, KCarry* __restrict__ kpart) {
-    __shared__ GCarry wl[GC_BLOCK / 64];
-    __shared__ KCarry wk[GC_BLOCK / 64];
-    const uint64_t t = (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x;
-    WCarry all;
-    wc_block_scan<RANKS>(wc_load<RANKS>(tail, ktail, t, t < ntiles), wl, wk, &all);
-    if (threadIdx.x == 0) wc_store<RANKS>(part, kpart, blockIdx.x, all);
-}
-
-// pexcl[b] = the parts in front of workgroup b combined (one workgroup)
-template <bool RANKS>
-__global__ void __launch_bounds__(GC_BLOCK)
-k_window_carry_pscan(const GCarry* __restrict__ part, const KCarry* __restrict__ kpart,
-                     uint32_t nb, GCarry* __restrict__ pexcl, KCarry* __restrict__ kpexcl) {
-    __shared__ GCarry wl[GC_BLOCK / 64];
-    __shared__ KCarry wk[GC_BLOCK / 64];
-    WCarry run{gc_none(), kc_none()};
-    if (threadIdx.x == 0) wc_store<RANKS>(pexcl, kpexcl, 0, run);
-    for (uint32_t r0 = 0; r0 < nb; r0 += GC_BLOCK) {
-        const uint32_t b = r0 + threadIdx.x;
-        WCarry all;
-        const WCarry inc = wc_block_scan<RANKS>(wc_load<RANKS>(part, kpart, b, b < nb), wl, wk,
-                                                &all);
-        if (b + 1 < nb) wc_store<RANKS>(pexcl, kpexcl, b + 1, wc_comb<RANKS>(run, inc));
-        run = wc_comb<RANKS>(run, all);
+struct WCarryTable {  // the two levels in parallel tables
+    GCarry* g;
+    KCarry* k;
+    __device__ __forceinline__ WCarry load(uint64_t i) const { return WCarry{g[i], k[i]}; }
+    __device__ __forceinline__ void store(uint64_t i, const WCarry& v) const {
+        g[i] = v.g;
+        k[i] = v.k;
     }
-}
-
-// carry[t] = the tails of all tiles in front of tile t combined
-template <bool RANKS>
-__global__ void __launch_bounds__(GC_BLOCK)
-k_window_carry_down(const GCarry* __restrict__ tail, const KCarry* __restrict__ ktail,
-                    uint64_t ntiles, const GCarry* __restrict__ pexcl,
-                    const KCarry* __restrict__ kpexcl, GCarry* __restrict__ carry,
-                    KCarry* __restrict__ kcarry) {
-    __shared__ GCarry wl[GC_BLOCK / 64];
-    __shared__ KCarry wk[GC_BLOCK / 64];
-    const uint64_t t = (uint64_t)blockIdx.x * GC_BLOCK + threadIdx.x;
-    WCarry all;
-    const WCarry inc =
-        wc_block_scan<RANKS>(wc_load<RANKS>(tail, ktail, t, t < ntiles), wl, wk, &all);
-    const WCarry front = wc_load<RANKS>(pexcl, kpexcl, blockIdx.x, true);
-    if (t == 0) wc_store<RANKS>(carry, kcarry, 0, front);
-    if (t + 1 < ntiles) wc_store<RANKS>(carry, kcarry, t + 1, wc_comb<RANKS>(front, inc));
-}
+};
 
 template <int AGG, bool RANKS>
 __global__ void __launch_bounds__(GA_THREADS)
 k_window_write(const Tup* __restrict__ in, uint64_t n, uint32_t gsh,
                const uint64_t* __restrict__ base, const GCarry* __restrict__ carry,
                const KCarry* __restrict__ kcarry, WinCols cols) {
-    __shared__ WWave L[GA_WAVES];
+    __shared__ GWave L[GA_WAVES];
+    __shared__ KCarry LK[RANKS ? GA_WAVES : 1];
     const int lane = lane_id(), w = threadIdx.x >> 6;
     const uint64_t cb = (uint64_t)blockIdx.x * GA_TILE + (uint64_t)w * GA_CHUNK;
-    const uint64_t le = lanemask_le();
     int64_t key[GA_IPT];
     MatVal pay[GA_IPT];
     uint64_t hb[GA_IPT], kb[GA_IPT];
     ga_load<AGG != 0>(in, n, cb, gsh, key, pay, hb);
     if (RANKS) wn_key_heads(in, n, cb, key, kb);
 
-    // per element, as offsets in the chunk (kNoOff: in front of it)
-    GAgg x[GA_IPT];          // aggregate from the element's group head, or the chunk's start
-    uint32_t so[GA_IPT];     // its group head
-    uint32_t ko[GA_IPT];     // its key head
-    uint32_t hrank[GA_IPT];  // group heads of the chunk at or before it
-    uint32_t dn[GA_IPT];     // key-only heads between its group head (the chunk's start) and it
-    GAgg run = ga_none();    // the open tail of the rounds so far
-    uint32_t rso = kNoOff, rko = kNoOff, heads = 0, drun = 0;
+    // per element (ga_walk), and as offsets in the chunk (kNoOff: in front of it)
+    GAgg x[GA_IPT];
+    uint32_t so[GA_IPT], hrank[GA_IPT];
+    uint32_t ko[GA_IPT];  // its key head
+    uint32_t dn[GA_IPT];  // key-only heads between its group head (the chunk's start) and it
+    const GWave mine = ga_walk<AGG>(n, cb, pay, hb, x, so, hrank);
+    if (lane == 0) L[w] = mine;
+    if (RANKS) {
+        const uint64_t le = lanemask_le();
+        uint32_t rko = kNoOff, drun = 0;
 #pragma unroll
-    for (int j = 0; j < GA_IPT; j++) {
-        const uint64_t hm = hb[j] & le;  // the round's group heads at or before this lane
-        const uint32_t seg = hm ? top_bit(hm) : 0;
-        if (AGG) {
-            GAgg v = cb + 64 * j + lane < n ? GAgg{(int64_t)pay[j], pay[j], pay[j]} : ga_none();
-            v = ga_seg_scan(v, lane - (int)seg);
-            if (!hm) v = ga_comb(run, v);
-            x[j] = v;
-            run = GAgg{last_lane(v.sum), last_lane(v.mn), last_lane(v.mx)};
-        }
-        so[j] = hm ? 64 * j + seg : rso;
-        hrank[j] = heads + (uint32_t)__popcll(hm);
-        if (RANKS) {
-            const uint64_t km = kb[j] & le;
+        for (int j = 0; j < GA_IPT; j++) {
+            const uint64_t hm = hb[j] & le, km = kb[j] & le;
             ko[j] = km ? 64 * j + top_bit(km) : rko;
             if (kb[j]) rko = 64 * j + top_bit(kb[j]);
             const uint64_t only = kb[j] & ~hb[j];
-            dn[j] = hm ? (uint32_t)__popcll(from_bit(only & le, seg))
+            dn[j] = hm ? (uint32_t)__popcll(from_bit(only & le, top_bit(hm)))
                        : drun + (uint32_t)__popcll(only & le);
             if (hb[j]) drun = (uint32_t)__popcll(from_bit(only, top_bit(hb[j])));
             else drun += (uint32_t)__popcll(only);
         }
-        if (hb[j]) rso = 64 * j + top_bit(hb[j]);
-        heads += (uint32_t)__popcll(hb[j]);
-    }
-    if (lane == 0) {
-        L[w].tail = GCarry{run.sum, AGG == 2 ? (int64_t)run.mn : 0, AGG == 2 ? (int64_t)run.mx : 0,
-                           rso == kNoOff ? kNoHead : cb + rso};
-        if (RANKS) L[w].k = KCarry{rko == kNoOff ? kNoHead : cb + rko, drun};
-        L[w].heads = heads;
+        if (lane == 0) LK[w] = KCarry{rko == kNoOff ? kNoHead : cb + rko, drun};
     }
     __syncthreads();
     // what comes in from the earlier tiles and the earlier waves of this one
     GCarry inc = carry[blockIdx.x];
-    KCarry kinc = kc_none();
-    if (RANKS) kinc = kcarry[blockIdx.x];
     uint64_t row = cols.group ? base[blockIdx.x] : 0;  // the group heads in front of the tile
+    KCarry kinc = kc_none();
+    if (RANKS) {
+        kinc = kcarry[blockIdx.x];
 #pragma unroll
-    for (int v = 0; v < GA_WAVES - 1; v++) {
-        if (v < w) {
-            if (RANKS) kinc = kc_comb(kinc, L[v].k, L[v].tail.start != kNoHead);
-            inc = gc_comb(inc, L[v].tail);
-            row += L[v].heads;
-        }
+        for (int v = 0; v < GA_WAVES - 1; v++)
+            if (v < w) kinc = kc_comb(kinc, LK[v], L[v].tail.start != kNoHead);
     }
+    ga_incoming(L, w, inc, row);
     const GAgg ia{inc.sum, (MatVal)inc.mn, (MatVal)inc.mx};
 #pragma unroll
     for (int j = 0; j < GA_IPT; j++) {
@@ -373,39 +255,10 @@ k_window_write(const Tup* __restrict__ in, uint64_t n, uint32_t gsh,
     }
 }
 
-// materialize.hip's tile table with 0 bounds words (`bounds` is unused and
-// equals `tot`) and, in tile_tab's extra bytes behind tot[0..1], the carry
-// step's tables, as groupagg.hip's GroupTab
-struct WindowTab : TileTab {
-    uint32_t nb;  // workgroups of the carry step
-    GCarry *tail, *carry, *part, *pexcl;
-    KCarry *ktail, *kcarry, *kpart, *kpexcl;  // null without RANKS
-};
-
-static WindowTab window_tab(Workspace* ws, uint64_t n, bool ranks) {
-    WindowTab g;
-    const uint64_t ntiles = (n + GA_TILE - 1) / GA_TILE;
-    g.nb = (uint32_t)((ntiles + GC_BLOCK - 1) / GC_BLOCK);
-    const size_t pad = ((3 * ntiles) & 1) * 8;  // the carry tables 16-aligned
-    const size_t items = 2 * ntiles + 2 * (size_t)g.nb;
-    static_cast<TileTab&>(g) = tile_tab(
-        ws, "window_tab", ntiles, 0,
-        pad + items * (sizeof(GCarry) + (ranks ? sizeof(KCarry) : 0)));
-    g.tail = (GCarry*)((char*)(g.tot + 2) + pad);
-    g.carry = g.tail + g.ntiles;
-    g.part = g.carry + g.ntiles;
-    g.pexcl = g.part + g.nb;
-    g.ktail = ranks ? (KCarry*)(g.pexcl + g.nb) : nullptr;
-    g.kcarry = ranks ? g.ktail + g.ntiles : nullptr;
-    g.kpart = ranks ? g.kcarry + g.ntiles : nullptr;
-    g.kpexcl = ranks ? g.kpart + g.nb : nullptr;
-    return g;
-}
-
 template <int AGG, bool RANKS>
 static void window_passes(Workspace* ws, const Tup* in, uint64_t n, uint32_t gsh,
                           const WinCols& cols, hipStream_t st) {
-    const WindowTab g = window_tab(ws, n, RANKS);
+    const TailTab g = tail_tab(ws, "window_tab", n, RANKS);
     const dim3 grid((uint32_t)g.ntiles), block(GA_THREADS);
     {
         TraceScope ts(ws, "k_window_count", st);
@@ -415,17 +268,13 @@ static void window_passes(Workspace* ws, const Tup* in, uint64_t n, uint32_t gsh
     }
     // the rows of the group table: only the group column reads them
     if (cols.group) mat_scan(ws, g.cnt, g.ntiles, g.base, g.ibase, g.tot, st);
-    {
-        TraceScope ts(ws, "k_window_carry", st);
-        hipLaunchKernelGGL(k_window_carry_part<RANKS>, dim3(g.nb), dim3(GC_BLOCK), 0, st, g.tail,
-                           g.ktail, g.ntiles, g.part, g.kpart);
-        SMJ_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_window_carry_pscan<RANKS>, dim3(1), dim3(GC_BLOCK), 0, st, g.part,
-                           g.kpart, g.nb, g.pexcl, g.kpexcl);
-        SMJ_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_window_carry_down<RANKS>, dim3(g.nb), dim3(GC_BLOCK), 0, st, g.tail,
-                           g.ktail, g.ntiles, g.pexcl, g.kpexcl, g.carry, g.kcarry);
-        SMJ_CHECK(hipGetLastError());
+    if constexpr (RANKS) {
+        typedef WCarryTable Tab;
+        carry_scan<WCarryOps>(ws, "k_window_carry", Tab{g.tail, g.ktail}, g.ntiles,
+                              Tab{g.part, g.kpart}, Tab{g.pexcl, g.kpexcl},
+                              Tab{g.carry, g.kcarry}, st);
+    } else {
+        tail_carry(ws, "k_window_carry", g, st);
     }
     TraceScope ts(ws, "k_window_write", st);
     hipLaunchKernelGGL((k_window_write<AGG, RANKS>), grid, block, 0, st, in, n, gsh, g.base,
@@ -441,15 +290,12 @@ void window(Workspace* ws, const Tup* in, uint64_t n, uint32_t group_shift, int6
     const int agg = (cols.mn || cols.mx) ? 2 : cols.sum ? 1 : 0;
     const bool ranks = cols.rank || cols.dense;
     if (n == 0 || !(agg || ranks || cols.group || cols.row)) return;
-    if (ranks) {
-        if (agg == 2) window_passes<2, true>(ws, in, n, group_shift, cols, st);
-        else if (agg == 1) window_passes<1, true>(ws, in, n, group_shift, cols, st);
-        else window_passes<0, true>(ws, in, n, group_shift, cols, st);
-    } else {
-        if (agg == 2) window_passes<2, false>(ws, in, n, group_shift, cols, st);
-        else if (agg == 1) window_passes<1, false>(ws, in, n, group_shift, cols, st);
-        else window_passes<0, false>(ws, in, n, group_shift, cols, st);
-    }
+    with_agg(agg, [&](auto A) {
+        with_flag(ranks, [&](auto R) {
+            window_passes<decltype(A)::value, decltype(R)::value>(ws, in, n, group_shift, cols,
+                                                                  st);
+        });
+    });
 }
 
 }  // namespace smj
